@@ -32,6 +32,10 @@ X3_MFMA_PEAK_TF = 2500.0 / 6       # fp32 product = 6 bf16 partial products on t
 H2_MFMA_PEAK_TF = 2500.0 / 3       # convs: fp32 product = 3 fp16 partial products (operands split into fp16 pairs)
 PRIMING_STEPS = int(os.environ.get("RCF_BENCH_PRIMING", "2"))   # untimed set-up steps before the warm-up (allocator / stream scratch)
 HBM_PEAK_GBS = 8000.0              # MI355X_MICROARCH.md: HBM3E, 8 TB/s
+BENCH_SEED = 7                     # torch's host generator, seeded at the start of every training leg (+ rank)
+DUMP_SAMPLE = 1 << 21              # --dump-outputs: parameter / gradient elements kept per leg (a fixed, seeded sample)
+DUMP_SAMPLE_SEED = 1234
+DUMP_MAX_BYTES = 64 << 20
 
 
 def main():
@@ -47,7 +51,11 @@ def main():
     ap.add_argument("--no-stage2", action="store_true")
     ap.add_argument("--no-bf16", action="store_true")
     ap.add_argument("--no-fp16", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what each training leg's last timed step computed as DIR/<name>.npy")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` without a launcher: start the N ranks ourselves.  The parent has not touched the GPU
@@ -97,10 +105,13 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
+    dumps = {}                                      # --dump-outputs: name -> array, filled by step_leg on rank 0
+
     def step_leg(precision, family, steps, warmup):
         """One training configuration: PRIMING_STEPS + warmup untimed steps, then `steps` timed ones between barriers
         (max over ranks), `family` bracketed live inside the timed region; then two more steps with EVERY conv family
         bracketed (roofline_by_kernel)."""
+        torch.manual_seed(BENCH_SEED + rank)        # Dropout2d's draws come from torch's host generator: same inputs every run
         model = rcf_amd.RCFModel(args, **config.stage1_model_kwargs(mask, dropout=0.1, norm="SyncBN"))
         shapes = {k: tuple(v.shape) for k, v in model.state_dict().items()}
         model.load_state_dict({k: torch.from_numpy(v) for k, v in synth.fill_state_dict(shapes, seed=7).items()})
@@ -121,6 +132,8 @@ def main():
         barrier()
         dt = time.perf_counter() - t0
         prof = ops.PROFILE.stop()
+        if a.dump_outputs and rank == 0:
+            dumps.update(last_step_outputs(precision, losses, trainer))
         if scaler is not None:
             step_leg.fp16_info = {"loss_scale_log2": int(round(float(np.log2(scaler.scale)))), "skipped_steps_in_timed_region": scaler.skipped - skipped0,
                                   "skipped_steps_before": skipped0}
@@ -243,6 +256,8 @@ def main():
         out["fp16_frames_per_s"], out["fp16_ms_per_step"] = f16["frames_per_s"], f16["ms_per_step"]
     if comm32:
         out["comm"] = comm32
+    if dumps:
+        out["dump_outputs"] = write_outputs(a.dump_outputs, dumps)
     if rank == 0:
         traffic = None          # HBM bytes per launch from the committed rocprofv3 PMC passes (same workload)
         tpath = os.path.join(ROOT, "profiles", "pmc_traffic.json")
@@ -458,6 +473,37 @@ def emit(out):
         print(f"bench_detail.json not written: {e}", file=sys.stderr)
     print("BENCH_DETAIL " + full, flush=True)
     print(fit_contract_line(contract_line(out)), flush=True)
+
+
+def last_step_outputs(prefix, losses, trainer):
+    """--dump-outputs: what a training step hands its caller, as float32 arrays named <prefix>_<what> -- every entry of the loss
+    dict, and the updated parameters and their gradients at DUMP_SAMPLE fixed, seeded positions of the trainable elements (the
+    flat buffers' alignment padding is never sampled; positions follow the flat buffers' own order)"""
+    import numpy as np
+    import torch
+    out = {f"{prefix}_{k}": np.asarray(v.detach().float().cpu().numpy() if torch.is_tensor(v) else v, dtype=np.float32)
+           for k, v in losses.items()}
+    fp = trainer.fp
+    sizes = np.array([p.numel() for p in fp.params], dtype=np.int64)
+    starts = np.cumsum(sizes) - sizes
+    n = int(sizes.sum())
+    pick = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(n, min(DUMP_SAMPLE, n), replace=False))
+    which = np.searchsorted(starts, pick, side="right") - 1
+    idx = torch.from_numpy(np.asarray(fp.offsets, dtype=np.int64)[which] + (pick - starts[which])).to(fp.flat.device)
+    out[f"{prefix}_params_sample"] = fp.flat[idx].cpu().numpy()
+    out[f"{prefix}_grads_sample"] = fp.grad[idx].cpu().numpy()
+    return out
+
+
+def write_outputs(d, arrays):
+    """arrays -> d/<name>.npy; -> a summary for bench_detail.json"""
+    import numpy as np
+    nbytes = sum(v.nbytes for v in arrays.values())
+    assert nbytes <= DUMP_MAX_BYTES, f"--dump-outputs: {nbytes} bytes > {DUMP_MAX_BYTES}"
+    os.makedirs(d, exist_ok=True)
+    for name, v in arrays.items():
+        np.save(os.path.join(d, name + ".npy"), v)
+    return {"dir": d, "arrays": sorted(arrays), "bytes": nbytes}
 
 
 def _free_port():

@@ -13,7 +13,7 @@ import rcf_torch as orc
 from rcf_amd import config, synth
 from rcf_amd.trainer import FlatParams
 
-REF_CFG = "/root/reference/configs/rcf/rcf_stage1.yaml"
+REF_CFG = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "rcf_stage1.yaml")   # the reference's configs/rcf/rcf_stage1.yaml
 
 
 def _args():
@@ -35,7 +35,6 @@ def test_yaml_loader_base_config_and_opts(tmp_path):
         config.load_args(str(child), ["missing.key", "1"])
 
 
-@pytest.mark.skipif(not os.path.exists(REF_CFG), reason="reference configs only exist in the build container")
 def test_reference_stage1_yaml_builds_the_model():
     """the reference's own YAML drives the constructor unchanged (mask size aside)"""
     args = config.load_args(REF_CFG, ["model_kwargs.mask_size", "[24, 40]"]) if False else config.load_args(REF_CFG)
@@ -88,6 +87,31 @@ def test_flat_params_views_and_zero_init():
         if isinstance(mod, Conv2d) and mod.cin % 4 == 0 and mod.weight.requires_grad:
             assert mod.weight.permute(0, 2, 3, 1).is_contiguous()
             assert mod.weight.grad.permute(0, 2, 3, 1).is_contiguous()
+
+
+def test_bench_dump_outputs_sample(tmp_path):
+    """bench.py --dump-outputs: the parameter / gradient sample lands on trainable elements only (never the flat buffers'
+    alignment padding), at the same positions every run, and the three training legs' arrays fit the 64 MB bound"""
+    import bench
+    m = rcf_amd.RCFModel(_args(), **config.stage1_model_kwargs((24, 40), dropout=0.0))
+    fp = FlatParams(m, torch.device("cpu"))
+    fp.flat.fill_(float("nan"))
+    fp.grad.fill_(float("nan"))
+    for i, (p, g) in enumerate(zip(fp.params, fp.grad_views)):
+        p.data.fill_(i)
+        g.fill_(-i)
+    trainer = types.SimpleNamespace(fp=fp)
+    losses = {"loss": torch.tensor(2.5), "loss_warp_seg": torch.tensor(1.5)}
+    a, b = bench.last_step_outputs("fp32", losses, trainer), bench.last_step_outputs("fp32", losses, trainer)
+    s, g = a["fp32_params_sample"], a["fp32_grads_sample"]
+    assert s.dtype == g.dtype == np.float32 and s.shape == g.shape == (bench.DUMP_SAMPLE,)
+    assert np.isfinite(s).all() and np.array_equal(g, -s) and np.array_equal(s, b["fp32_params_sample"])
+    assert len(np.unique(s)) > len(fp.params) // 2                     # spread over the parameters, not one tensor
+    assert a["fp32_loss"].dtype == np.float32 and float(a["fp32_loss_warp_seg"]) == 1.5
+    legs = {f"{leg}_{k[5:]}": v for leg in ("fp32", "bf16", "fp16") for k, v in a.items()}
+    info = bench.write_outputs(str(tmp_path / "dump"), legs)
+    assert info["bytes"] <= 64 << 20 and sorted(os.listdir(tmp_path / "dump")) == sorted(n + ".npy" for n in legs)
+    assert np.array_equal(np.load(tmp_path / "dump" / "bf16_params_sample.npy"), s)
 
 
 def test_synthetic_data_is_deterministic_and_well_formed():
