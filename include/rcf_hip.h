@@ -687,6 +687,14 @@ int rcf_dropout2d_scale_f32(float *out, long n, float p, unsigned long long seed
 int rcf_eval_iou_counts_f32(const float *masks, const uint8_t *ann, int B, int C, int h, int w, int H, int W, float pos_th,
                             unsigned long long *counts, void *stream);
 
+/* ---- DAVIS J & F counts (tools/davis2016-evaluation/davis2017/metrics.py) ----------------------------------------------
+ * pred, gt, void_px u8 [N][H][W], any nonzero byte = on; void_px NULL = no void pixels.  counts [N][6] int64, zero-filled by
+ * the caller: inter, union (db_eval_iou), n_fg, n_gt, fg_match, gt_match (f_measure: boundary pixels of _seg2bmap(mask & !void)
+ * and those within the disk X^2+Y^2 <= radius^2 of a boundary pixel of the other map).  RCF_EINVAL for radius outside
+ * [0, 64], N, H or W <= 0, or a NULL pred / gt / counts, before any launch. */
+int rcf_davis_counts_u8(const uint8_t *pred, const uint8_t *gt, const uint8_t *void_px, int N, int H, int W, int radius,
+                        long long *counts, void *stream);
+
 /* ---- data transform on the device ------------------------------------------------------
  * dataset/transforms.py:884-924 `Transform` (Resize :170-237 -> RandomCrop :442-508 -> RandomFlip :249-306 ->
  * PhotoMetricDistortion :557-687 -> FlowTransform :825-848 / PLTransform :865-876 -> NumpyToTensor :793-808 ->

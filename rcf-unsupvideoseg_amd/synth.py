@@ -169,6 +169,113 @@ def eval_inputs(seed, N=6, C=4, h=30, w=54, H=120, W=214):
     return masks, ann, names
 
 
+DAVIS_KINDS = ("blobs", "empty_pred", "empty_gt", "both_empty", "all_ones", "pixels", "lines", "checker")
+
+
+def _davis_blobs(g, H, W):
+    """u8 [H,W]: integer discs, rectangles, 1-px lines and sparse noise -- no pixel sits on a float threshold"""
+    m = np.zeros((H, W), dtype=np.uint8)
+    yy, xx = np.ogrid[:H, :W]
+    for _ in range(int(g.integers(1, 4))):
+        cy, cx = int(g.integers(0, H)), int(g.integers(0, W))
+        rr = int(g.integers(1, max(2, min(H, W) // 3)))
+        m[(yy - cy) ** 2 + (xx - cx) ** 2 <= rr * rr] = 1
+    for _ in range(int(g.integers(0, 3))):
+        y0, x0 = int(g.integers(0, H)), int(g.integers(0, W))
+        m[y0:y0 + int(g.integers(1, H + 1)), x0:x0 + int(g.integers(1, W + 1))] ^= 1
+    if H > 2 and W > 2:
+        m[int(g.integers(0, H)), :] ^= 1
+        m[:, int(g.integers(0, W))] ^= 1
+    m[g.integers(0, 1000, size=(H, W)) < 3] ^= 1
+    return m
+
+
+def davis_inputs(seed, N=1, H=480, W=854, kind="blobs", void=False):
+    """Inputs of the DAVIS-metric fixtures (tests/golden/make_golden_davis.py): pred, gt u8 [N,H,W] in {0,1} and, with
+    `void`, a u8 [N,H,W] void mask (a rectangle plus sparse pixels), else None.  Integer arithmetic only."""
+    g = _rng(seed)
+    pred, gt = np.zeros((N, H, W), dtype=np.uint8), np.zeros((N, H, W), dtype=np.uint8)
+    for n in range(N):
+        if kind == "blobs":
+            gt[n] = _davis_blobs(g, H, W)
+            pred[n] = gt[n].copy()
+            dy, dx = int(g.integers(-3, 4)), int(g.integers(-3, 4))
+            pred[n] = np.roll(pred[n], (dy, dx), axis=(0, 1))
+            pred[n] ^= (_davis_blobs(g, H, W) & (g.integers(0, 4, size=(H, W)) == 0)).astype(np.uint8)
+        elif kind in ("empty_pred", "empty_gt"):
+            m = _davis_blobs(g, H, W)
+            (gt if kind == "empty_pred" else pred)[n] = m
+        elif kind == "all_ones":
+            pred[n], gt[n] = 1, 1
+        elif kind == "pixels":                       # single pixels in the corners and on the edges
+            for y, x in ((0, 0), (0, W - 1), (H - 1, 0), (H - 1, W - 1)):
+                (pred if g.integers(0, 2) else gt)[n, y, x] = 1
+            for _ in range(4):
+                pred[n, 0, int(g.integers(0, W))] = 1
+                gt[n, H - 1, int(g.integers(0, W))] = 1
+                pred[n, int(g.integers(0, H)), W - 1] = 1
+                gt[n, int(g.integers(0, H)), 0] = 1
+        elif kind == "lines":                        # 1-px lines: horizontal, vertical, diagonal
+            for a in (pred[n], gt[n]):
+                a[int(g.integers(0, H)), :] = 1
+                a[:, int(g.integers(0, W))] = 1
+                k = int(g.integers(-W, H))
+                yy, xx = np.ogrid[:H, :W]
+                a[(yy - xx) == k] = 1
+        elif kind == "checker":
+            yy, xx = np.ogrid[:H, :W]
+            gt[n] = ((yy + xx) % 2).astype(np.uint8)
+            pred[n] = (((yy // 2) + (xx // 3)) % 2).astype(np.uint8)
+        elif kind != "both_empty":
+            raise ValueError(f"unknown kind {kind}")
+    vd = None
+    if void:
+        vd = (g.integers(0, 200, size=(N, H, W)) == 0).astype(np.uint8)
+        y0, x0 = int(g.integers(0, H)), int(g.integers(0, W))
+        vd[:, y0:y0 + max(1, H // 4), x0:x0 + max(1, W // 5)] = 1
+    return pred, gt, vd
+
+
+DAVIS_TREE = (("bear", 6, None), ("car-turn", 5, (240, 427)), ("dance", 7, None))   # (sequence, frames, export size)
+
+
+def davis_tree(root, seed=2016, step=0):
+    """A synthetic DAVIS-2016 tree under `root`: ImageSets/480p/val.txt, JPEGImages/480p (tiny placeholder files: only
+    their number is read), Annotations/480p (u8 PNG, 0 / 255, 480x854) and, under root/results, the exported
+    pred_seg_{seq}_{id}_{step:07}.png masks (RGB PNG; one sequence exported at 240x427, so the evaluator resizes it).
+    Returns (davis_path, results_path)."""
+    import os
+    from PIL import Image
+    g = _rng(seed)
+    res = os.path.join(root, "results")
+    os.makedirs(os.path.join(root, "ImageSets", "480p"), exist_ok=True)
+    os.makedirs(res, exist_ok=True)
+    lines = []
+    for si, (seq, T, size) in enumerate(DAVIS_TREE):
+        for d in ("JPEGImages", "Annotations"):
+            os.makedirs(os.path.join(root, d, "480p", seq), exist_ok=True)
+        _, gt, _ = davis_inputs(seed + si, N=T, H=480, W=854, kind="blobs")
+        for t in range(T):
+            fid = f"{t:05d}"
+            lines.append(f"/JPEGImages/480p/{seq}/{fid}.jpg /Annotations/480p/{seq}/{fid}.png\n")
+            with open(os.path.join(root, "JPEGImages", "480p", seq, fid + ".jpg"), "wb") as f:
+                f.write(b"placeholder")
+            Image.fromarray(gt[t] * 255).save(os.path.join(root, "Annotations", "480p", seq, fid + ".png"))
+            # prediction: the annotation shifted, with a blob toggled; u8 0 / 255 with a few mid-grey pixels
+            p = np.roll(gt[t], (int(g.integers(-6, 7)), int(g.integers(-6, 7))), axis=(0, 1)) * 255
+            p[(_davis_blobs(g, 480, 854) == 1) & (g.integers(0, 3, size=(480, 854)) == 0)] ^= 255
+            p[g.integers(0, 50, size=(480, 854)) == 0] = 128
+            if si == 1 and t == 2:
+                p[:] = 0                                           # an empty prediction frame
+            img = Image.fromarray(np.stack([p, p, p], -1).astype(np.uint8))
+            if size is not None:
+                img = img.resize((size[1], size[0]), resample=Image.NEAREST)
+            img.save(os.path.join(res, f"pred_seg_{seq}_{fid}_{step:07}.png"))
+    with open(os.path.join(root, "ImageSets", "480p", "val.txt"), "w") as f:
+        f.writelines(lines)
+    return root, res
+
+
 def fill_state_dict(shapes, seed=7, bn3_gamma=0.5, seg_scale=10.0):
     """Seeded weights for every entry of a state-dict `shapes` mapping name -> shape.
 
