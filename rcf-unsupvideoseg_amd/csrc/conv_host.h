@@ -1,0 +1,74 @@
+// Host-side launch helpers shared by the conv entry points of csrc/igemm_conv.hip (fp32 tensors) and csrc/igemm_bf16.hip
+// (16-bit tensors): shape and region checks, region -> kernel parameters, the split-K plan of the weight gradients.
+// No device code; included by those two files only.
+#pragma once
+#include <math.h>
+#include "rcf_common.h"
+
+// what check_shape of both files asks of a rcf_conv_shape before its own alignment rules
+static inline int conv_check_geometry(const rcf_conv_shape *s) {
+    if (!s || s->struct_bytes != sizeof(rcf_conv_shape)) return RCF_EINVAL;      // a caller built against another header
+    if (s->N <= 0 || s->H <= 0 || s->W <= 0 || s->Cin <= 0 || s->Cout <= 0 || s->R <= 0 || s->S <= 0) return RCF_EINVAL;
+    if (s->stride <= 0 || s->dil <= 0 || s->pad < 0) return RCF_EINVAL;
+    const int ho = (s->H + 2 * s->pad - s->dil * (s->R - 1) - 1) / s->stride + 1;
+    const int wo = (s->W + 2 * s->pad - s->dil * (s->S - 1) - 1) / s->stride + 1;
+    if (ho != s->Ho || wo != s->Wo) return RCF_EINVAL;
+    if ((long)s->N * s->Ho * s->Wo >= (1L << 31) || (long)s->N * s->H * s->W >= (1L << 31)) return RCF_EINVAL;
+    return 0;
+}
+
+static inline unsigned magic_of(int d) { return d <= 1 ? 0u : (unsigned)((1ull << 32) / (unsigned)d + 1ull); }
+
+static inline bool korder_chunked(unsigned flags) { return !(flags & RCF_CONV_KORDER_NATURAL); }
+
+// rectangle (or frame of width `band`) of a [N, H, W] tensor; null = everything
+static inline bool region_ok(const rcf_conv_region *r, int H, int W) {
+    return !r || (r->y0 >= 0 && r->x0 >= 0 && r->h > 0 && r->w > 0 && r->y0 + r->h <= H && r->x0 + r->w <= W &&
+                  r->band >= 0 && (r->band == 0 || (2 * r->band < r->h && 2 * r->band < r->w)));
+}
+
+static inline int region_pixels(const rcf_conv_region *r, int H, int W) {       // contributing pixels per image
+    if (!r) return H * W;
+    return r->band > 0 ? 2 * r->band * r->w + 2 * r->band * (r->h - 2 * r->band) : r->h * r->w;
+}
+
+// the region fields of a weight-gradient launch (WgradParams of either file); the caller checked region_ok over Ho x Wo
+template <class P>
+static inline void fill_region(P &p, const rcf_conv_region *r, int N, int H, int W) {
+    p.ry0 = r ? r->y0 : 0; p.rx0 = r ? r->x0 : 0; p.rh = r ? r->h : H; p.rw = r ? r->w : W;
+    p.rband = r ? r->band : 0;
+    p.rr = region_pixels(r, H, W);
+    p.M = (decltype(p.M))N * p.rr;
+}
+
+// the same for the GEMM rows [N, H, W] of a forward or data-gradient launch (IgemmParams, ConvParams).  Returns 0 / RCF_EINVAL.
+template <class P>
+static inline int set_region(P &p, const rcf_conv_region *r, int N, int H, int W) {
+    if (!region_ok(r, H, W) || H <= 0 || W <= 0) return RCF_EINVAL;               // (no region: the whole tensor, not an empty one)
+    fill_region(p, r, N, H, W);
+    return 0;
+}
+
+// Split K (the M pixels) of a weight gradient over `c` workgroups per tile, c in 1..hi, on `slots` resident workgroups.  Cost
+// model in microseconds: rounds(c) x pixels per workgroup x time per pixel (px_us) + the fixed-order reduction, which reads c
+// copies of the weight gradient (wbytes each, ~2 bytes/us/1e6 effective).  Small weights on many pixels (layer1) want hundreds
+// of splits, large weights on few pixels (layer4) a handful.
+static inline long splitk_search(long tiles, long M, long slots, long hi, double px_us, double wbytes) {
+    double best = 1e30;
+    long sk = 1;
+    for (long c = 1; c <= hi; ++c) {
+        const double rounds = (double)((tiles * c + slots - 1) / slots);
+        const double cost = rounds * (double)((M + c - 1) / c) * px_us + (c > 1 ? (double)c * wbytes / 2.0e6 + 3.0 : 0.0);
+        if (cost < best - 1e-9) { best = cost; sk = c; }
+    }
+    return sk;
+}
+
+// 32-bit descriptor offsets: the images (and dy rows) one pixel chunk touches must span < 2 GiB.  Halves the chunk (kept a
+// multiple of `unit` pixels) until they do; RR = pixels per image, esize = bytes per element.
+static inline long splitk_chunk_fit(long chunk, long unit, long RR, const rcf_conv_shape *s, int esize) {
+    const long img_bytes = (long)s->H * s->W * s->x_pitch * esize, dy_bytes = (long)s->Ho * s->Wo * s->y_pitch * esize;
+    while (chunk > unit && ((chunk / RR + 2) * img_bytes >= (1L << 31) || (chunk / RR + 2) * dy_bytes >= (1L << 31)))
+        chunk = (chunk / 2 + unit - 1) / unit * unit;
+    return chunk;
+}

@@ -12,7 +12,7 @@
 // (ds_read_b128: lane = row, lane >> 5 = which half of a 16-k substep) bank-conflict free without padding.
 #include <cstdlib>
 #include <type_traits>
-#include "rcf_common.h"
+#include "conv_host.h"
 
 // No mutable process state: the A/B choices travel in rcf_conv_shape.flags (RCF_CONV_*), per call.
 
@@ -1209,58 +1209,14 @@ __global__ void __launch_bounds__(256, MR == 2 ? 2 : 1) wgrad_bf16_dma_kernel(Wg
     }
 }
 
-__global__ void splitk_reduce_kernel(const float *__restrict__ ws, float *__restrict__ dw, long n4, long stride,
-                                     int splits, int beta) {
-    long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    const long step = (long)gridDim.x * blockDim.x;
-    for (; i < n4; i += step) {
-        f32x4 a0 = beta ? reinterpret_cast<const f32x4 *>(dw)[i] : f32x4{0.f, 0.f, 0.f, 0.f};
-        f32x4 a1 = {0.f, 0.f, 0.f, 0.f}, a2 = a1, a3 = a1;
-        int s = 0;
-        for (; s + 3 < splits; s += 4) {
-            a0 += reinterpret_cast<const f32x4 *>(ws + (long)s * stride)[i];
-            a1 += reinterpret_cast<const f32x4 *>(ws + (long)(s + 1) * stride)[i];
-            a2 += reinterpret_cast<const f32x4 *>(ws + (long)(s + 2) * stride)[i];
-            a3 += reinterpret_cast<const f32x4 *>(ws + (long)(s + 3) * stride)[i];
-        }
-        for (; s < splits; ++s) a0 += reinterpret_cast<const f32x4 *>(ws + (long)s * stride)[i];
-        reinterpret_cast<f32x4 *>(dw)[i] = (a0 + a1) + (a2 + a3);
-    }
-}
-
-// ------------------------------------------------------------------------------------------- host side
+// ------------------------------------------------------------------------------------------- host side (+ conv_host.h)
 // cout_mult: 8 where Cout is read or written as bf16 (16-byte accesses), 4 for the forward with fp32 output
 int check_shape(const rcf_conv_shape *s, int cout_mult = 8) {
-    if (!s || s->struct_bytes != sizeof(rcf_conv_shape)) return RCF_EINVAL;      // a caller built against another header
-    if (s->N <= 0 || s->H <= 0 || s->W <= 0 || s->Cin <= 0 || s->Cout <= 0 || s->R <= 0 || s->S <= 0) return RCF_EINVAL;
+    if (int e = conv_check_geometry(s)) return e;
     // 16-byte loads of 8 bf16 channels: channel counts and pitches in multiples of 8
     if (s->Cin % 8 || s->Cout % cout_mult || s->x_pitch % 8 || s->x_pitch < s->Cin || s->y_pitch < s->Cout) return RCF_EINVAL;
-    if (s->stride <= 0 || s->dil <= 0 || s->pad < 0) return RCF_EINVAL;
-    const int ho = (s->H + 2 * s->pad - s->dil * (s->R - 1) - 1) / s->stride + 1;
-    const int wo = (s->W + 2 * s->pad - s->dil * (s->S - 1) - 1) / s->stride + 1;
-    if (ho != s->Ho || wo != s->Wo) return RCF_EINVAL;
-    if ((long)s->N * s->Ho * s->Wo >= (1L << 31) || (long)s->N * s->H * s->W >= (1L << 31)) return RCF_EINVAL;
     return 0;
 }
-
-inline unsigned magic_of(int d) { return d <= 1 ? 0u : (unsigned)((1ull << 32) / (unsigned)d + 1ull); }
-
-inline int region_pixels(const rcf_conv_region *r, int H, int W) {
-    if (!r) return H * W;
-    return r->band > 0 ? 2 * r->band * r->w + 2 * r->band * (r->h - 2 * r->band) : r->h * r->w;
-}
-
-int set_region(ConvParams &p, const rcf_conv_region *r, int N, int H, int W) {
-    p.ry0 = r ? r->y0 : 0; p.rx0 = r ? r->x0 : 0; p.rh = r ? r->h : H; p.rw = r ? r->w : W;
-    p.rband = r ? r->band : 0;
-    if (p.ry0 < 0 || p.rx0 < 0 || p.rh <= 0 || p.rw <= 0 || p.ry0 + p.rh > H || p.rx0 + p.rw > W) return RCF_EINVAL;
-    if (p.rband < 0 || (p.rband > 0 && (2 * p.rband >= p.rh || 2 * p.rband >= p.rw))) return RCF_EINVAL;
-    p.rr = region_pixels(r, H, W);
-    p.M = N * p.rr;
-    return 0;
-}
-
-inline bool korder_chunked(unsigned flags) { return !(flags & RCF_CONV_KORDER_NATURAL); }
 
 // LDS-DMA kernels (128x64 / 128x128 / 128x256 by output width), three stages, pieces interleaved with the MFMAs
 template <int MR, int NR, int WM, int WN, bool OBF>
@@ -1327,35 +1283,16 @@ WgradPlan plan_wgrad(const rcf_conv_shape *s, const rcf_conv_region *reg) {
     const long RR = region_pixels(reg, s->Ho, s->Wo);
     const long M = (long)s->N * RR;
     const long tiles = (long)pl.itiles * pl.jtiles;
-    // Split K (the pixels) over `c` workgroups per tile; 2 workgroups per CU = 512 slots.  Cost model in microseconds:
-    // rounds(c) x pixels per workgroup x time per pixel (0.025 us for the 128x256 tile at the measured ~30 % of the MFMA
-    // peak, proportionally less for smaller tiles down to the load-bound floor) + the fixed-order reduction, which reads
-    // c copies of the weight gradient (~2 bytes/us/1e6 effective).  Small weights on many pixels (layer1) want hundreds
-    // of splits, large weights on few pixels (layer4) a handful.
+    // Split K (the pixels) over the workgroups of a tile (splitk_search); 2 workgroups per CU = 512 slots.  Time per pixel:
+    // 0.025 us for the 128x256 tile at the measured ~30 % of the MFMA peak, proportionally less for smaller tiles down to
+    // the load-bound floor.
     const double px_us = 0.025 * fmax((double)(pl.mr * pl.nr) / 8.0, 0.35);
-    const double wbytes = (double)s->Cout * ktot * 4.0;
     const long maxsk = M / 512 > 1 ? M / 512 : 1;
-    const long slots = 512, hi = maxsk < 256 ? maxsk : 256;
-    double best = 1e30;
-    long sk = 1;
-    for (long c = 1; c <= hi; ++c) {
-        const double rounds = (double)((tiles * c + slots - 1) / slots);
-        const double cost = rounds * (double)((M + c - 1) / c) * px_us + (c > 1 ? (double)c * wbytes / 2.0e6 + 3.0 : 0.0);
-        if (cost < best - 1e-9) { best = cost; sk = c; }
-    }
-    long chunk = (M + sk - 1) / sk;
-    chunk = (chunk + 31) / 32 * 32;
-    const long img_bytes = (long)s->H * s->W * s->x_pitch * 2, dy_bytes = (long)s->Ho * s->Wo * s->y_pitch * 2;
-    while (chunk > 32 && ((chunk / RR + 2) * img_bytes >= (1L << 31) || (chunk / RR + 2) * dy_bytes >= (1L << 31)))
-        chunk = (chunk / 2 + 31) / 32 * 32;
+    const long sk = splitk_search(tiles, M, 512, maxsk < 256 ? maxsk : 256, px_us, (double)s->Cout * ktot * 4.0);
+    const long chunk = splitk_chunk_fit(((M + sk - 1) / sk + 31) / 32 * 32, 32, RR, s, 2);
     pl.splitk = (int)((M + chunk - 1) / chunk);
     pl.chunk = chunk;
     return pl;
-}
-
-bool region_ok(const rcf_conv_region *r, int H, int W) {
-    return !r || (r->y0 >= 0 && r->x0 >= 0 && r->h > 0 && r->w > 0 && r->y0 + r->h <= H && r->x0 + r->w <= W &&
-                  r->band >= 0 && (r->band == 0 || (2 * r->band < r->h && 2 * r->band < r->w)));
 }
 
 }  // namespace
@@ -1591,10 +1528,8 @@ extern "C" int rcf_conv2d_wgrad_bf16(const void *x, const void *dy, float *dw, c
     p.Cout = s->Cout; p.Cin = s->Cin; p.R = s->R; p.S = s->S;
     p.H = s->H; p.W = s->W; p.Ho = s->Ho; p.Wo = s->Wo; p.stride = s->stride; p.pad = s->pad; p.dil = s->dil;
     p.x_pitch = s->x_pitch; p.dy_pitch = s->y_pitch;
-    p.ry0 = region ? region->y0 : 0; p.rx0 = region ? region->x0 : 0;
-    p.rh = region ? region->h : s->Ho; p.rw = region ? region->w : s->Wo;
-    p.rband = region ? region->band : 0; p.rr = region_pixels(region, s->Ho, s->Wo);
-    p.M = (long)s->N * p.rr; p.chunk = pl.chunk; p.itiles = pl.itiles; p.jtiles = pl.jtiles;
+    fill_region(p, region, s->N, s->Ho, s->Wo);
+    p.chunk = pl.chunk; p.itiles = pl.itiles; p.jtiles = pl.jtiles;
     p.split_stride = (long)s->Cout * s->R * s->S * s->Cin; p.beta = beta;
     p.Ktot = s->R * s->S * s->Cin;
     p.sched = 1;
@@ -1623,13 +1558,6 @@ extern "C" int rcf_conv2d_wgrad_bf16(const void *x, const void *dy, float *dw, c
 #undef RCF_WG
 #undef RCF_WGD
     RCF_LAUNCH_CHECK();
-    if (pl.splitk > 1) {
-        const long n4 = p.split_stride / 4;
-        const int bt = n4 < (1 << 17) ? 64 : 256;
-        const int blocks = (int)((n4 + bt - 1) / bt < 4096 ? (n4 + bt - 1) / bt : 4096);
-        hipLaunchKernelGGL(splitk_reduce_kernel, dim3(blocks), dim3(bt), 0, st, (const float *)workspace, dw, n4,
-                           p.split_stride, pl.splitk, beta);
-        RCF_LAUNCH_CHECK();
-    }
+    if (pl.splitk > 1) return rcf_splitk_reduce((const float *)workspace, dw, p.split_stride, p.split_stride, pl.splitk, beta, stream);
     return 0;
 }

@@ -20,7 +20,7 @@
 // 8 consecutive ids take 8 different row tiles and ids b, b+8, b+16.. walk the column tiles of the
 // same row tile: the activation tile is re-read from that XCD's own L2.
 #include <type_traits>
-#include "rcf_common.h"
+#include "conv_host.h"
 
 #include <cstdlib>
 
@@ -2003,17 +2003,13 @@ __global__ void splitk_reduce_kernel(const float *__restrict__ ws, float *__rest
     }
 }
 
+// host side from here on (+ conv_host.h)
 int check_shape(const rcf_conv_shape *s) {
-    if (!s || s->struct_bytes != sizeof(rcf_conv_shape)) return RCF_EINVAL;      // a caller built against another header
-    if (s->N <= 0 || s->H <= 0 || s->W <= 0 || s->Cin <= 0 || s->Cout <= 0 || s->R <= 0 || s->S <= 0) return RCF_EINVAL;
+    if (int e = conv_check_geometry(s)) return e;
     if (s->Cin % 4 || s->x_pitch % 4 || s->y_pitch % 4 || s->x_pitch < s->Cin || s->y_pitch < s->Cout) return RCF_EINVAL;
-    if (s->stride <= 0 || s->dil <= 0 || s->pad < 0) return RCF_EINVAL;
-    const int ho = (s->H + 2 * s->pad - s->dil * (s->R - 1) - 1) / s->stride + 1;
-    const int wo = (s->W + 2 * s->pad - s->dil * (s->S - 1) - 1) / s->stride + 1;
-    if (ho != s->Ho || wo != s->Wo) return RCF_EINVAL;
-    if ((long)s->N * s->Ho * s->Wo >= (1L << 31) || (long)s->N * s->H * s->W >= (1L << 31)) return RCF_EINVAL;
     return 0;
 }
+
 
 // RCF_CONV_FP32_MFMA(v) in the call's flags: the fp32-MFMA kernels with tuning variant v (bit 0: K-step 32, bit 1: row-major
 // LDS tiles) instead of the fp16-pair / bf16-triple kernels; -1 = not asked for
@@ -2022,9 +2018,6 @@ inline bool use_x3(unsigned flags) { return fp32_mfma_variant(flags) < 0; }
 // thin 1x1 convs (<= 16 output channels) leave the GEMM kernels for csrc/thin.hip's streaming passes -- on the default path only:
 // the RCF_CONV_FP32_MFMA test variants keep the kernels they are there to exercise
 inline bool thin_path(const rcf_conv_shape *s) { return use_x3(s->flags) && !(s->flags & RCF_CONV_NO_THIN) && rcf_thin_ok(s); }
-inline bool korder_chunked(unsigned flags) { return !(flags & RCF_CONV_KORDER_NATURAL); }
-
-inline unsigned magic_of(int d) { return d <= 1 ? 0u : (unsigned)((1ull << 32) / (unsigned)d + 1ull); }
 
 template <int BMODE, int BKT, bool RM>
 int launch_igemm_v(IgemmParams &p, hipStream_t st) {
@@ -2108,6 +2101,13 @@ int h2p_stat_rows(int M, int gn) {                        // partial statistics 
 // is the plane-separated (LDS-image) half of a rcf_conv_weight_pairs2_f32 buffer written for this shape?  Whenever the kernels
 // that read it by LDS-DMA (conv_h2p_kernel, conv_h2d_kernel) can take the shape at all: whole K-steps that do not straddle a tap
 bool pairs2_written(int K, int Cs) { return K % 16 == 0 && Cs % 16 == 0; }
+
+// can this data gradient take the lean epilogue of the 128-row fp16-pair kernels (the batch-norm backward sums, the masked
+// addend)?  Whole column tiles, operand ranges, weights prepared by the caller.  Its users add: the whole tensor, no region.
+bool dgrad_lean_ok(const rcf_conv_shape *s) {
+    const int bnw = s->Cin > 128 ? 256 : (s->Cin > 64 ? 128 : 64);
+    return use_x3(s->flags) && s->Cin % bnw == 0 && (s->w_pairs2_t || s->w_pairs_t) && s->amax_dy && s->amax_w;
+}
 
 bool h2p_eligible(const IgemmParams &p, int batches) {
     if ((p.flags & RCF_CONV_H2P_NEVER) || !p.b_pairs2 || !p.amax_a || !p.amax_b || batches != 1 || p.batch1 > 0) return false;
@@ -2220,11 +2220,6 @@ int launch_igemm(IgemmParams &p, hipStream_t st) {
     }
 }
 
-inline int region_pixels(const rcf_conv_region *r, int H, int W) {
-    if (!r) return H * W;
-    return r->band > 0 ? 2 * r->band * r->w + 2 * r->band * (r->h - 2 * r->band) : r->h * r->w;
-}
-
 struct WgradPlan {
     int mr, nr, itiles, jtiles, splitk;
     long chunk;
@@ -2265,60 +2260,26 @@ WgradPlan plan_wgrad(const rcf_conv_shape *s, const rcf_conv_region *reg = nullp
     if (x3 && !smallc && pl.mr >= 2 && pl.nr >= 2) {
         // the split-bf16 kernel runs 3 workgroups per CU (768 slots): pick the split whose last round is fullest
         // (time ~ rounds / split; the fixed-order reduction costs ~ split)
-        const long slots = pl.mr == 4 ? 256 : (pl.nr == 4 ? 512 : 768), hi = maxsk < 256 ? maxsk : 256;   // (the 128 x 256 kernel: 2 per CU = 512; 256 x 256: 1)
-        double best = 1e30;
-        {
-            // the cost model of the bf16 weight gradient (csrc/igemm_bf16.hip), in microseconds: rounds x pixels per
-            // workgroup x time per pixel (three partial products: 3 x the bf16 figure) + the fixed-order reduction, which
-            // reads c copies of the weight gradient
-            const double px_us = 0.075 * fmax((double)(pl.mr * pl.nr) / 8.0, 0.35);
-            const double wbytes = (double)s->Cout * s->R * s->S * s->Cin * 4.0;
-            for (long c = 1; c <= hi; ++c) {
-                const double rounds = (double)((tiles * c + slots - 1) / slots);
-                const double cost = rounds * (double)((M + c - 1) / c) * px_us + (c > 1 ? (double)c * wbytes / 2.0e6 + 3.0 : 0.0);
-                if (cost < best - 1e-9) { best = cost; sk = c; }
-            }
-        }
+        const long slots = pl.mr == 4 ? 256 : (pl.nr == 4 ? 512 : 768);   // (the 128 x 256 kernel: 2 per CU = 512; 256 x 256: 1)
+        // time per pixel: three partial products, 3 x the figure of the bf16 weight gradient (csrc/igemm_bf16.hip)
+        const double px_us = 0.075 * fmax((double)(pl.mr * pl.nr) / 8.0, 0.35);
+        sk = splitk_search(tiles, M, slots, maxsk < 256 ? maxsk : 256, px_us, (double)s->Cout * s->R * s->S * s->Cin * 4.0);
     }
-    long chunk = (M + sk - 1) / sk;
-    chunk = (chunk + BK - 1) / BK * BK;
-    if (x3 && !smallc) {
-        // 32-bit descriptor offsets: the images (and dy rows) one pixel chunk touches must span < 2 GiB
-        const long img_bytes = (long)s->H * s->W * s->x_pitch * 4, dy_bytes = (long)s->Ho * s->Wo * s->y_pitch * 4;
-        while (chunk > BK && ((chunk / RR + 2) * img_bytes >= (1L << 31) || (chunk / RR + 2) * dy_bytes >= (1L << 31)))
-            chunk = (chunk / 2 + BK - 1) / BK * BK;
-    }
+    long chunk = ((M + sk - 1) / sk + BK - 1) / BK * BK;
+    if (x3 && !smallc) chunk = splitk_chunk_fit(chunk, BK, RR, s, 4);
     sk = (M + chunk - 1) / chunk;
     pl.splitk = (int)sk;
     pl.chunk = chunk;
     return pl;
 }
 
-}  // namespace
-
-namespace {
-// rectangle (or frame) of the GEMM-row tensor [N, H, W]; null = everything.  Returns 0 / RCF_EINVAL.
-int set_region(IgemmParams &p, const rcf_conv_region *r, int N, int H, int W) {
-    p.ry0 = r ? r->y0 : 0; p.rx0 = r ? r->x0 : 0; p.rh = r ? r->h : H; p.rw = r ? r->w : W;
-    p.rband = r ? r->band : 0;
-    if (p.ry0 < 0 || p.rx0 < 0 || p.rh <= 0 || p.rw <= 0 || p.ry0 + p.rh > H || p.rx0 + p.rw > W) return RCF_EINVAL;
-    if (p.rband < 0 || (p.rband > 0 && (2 * p.rband >= p.rh || 2 * p.rband >= p.rw))) return RCF_EINVAL;
-    p.rr = region_pixels(r, H, W);
-    p.M = N * p.rr;
-    return 0;
-}
-}  // namespace
-
-/* C[M][N] (pitch ldc) (+)= A[M][K] (pitch lda) . B[N][K]^T (pitch ldb) + bias[N], then act (0 none, 1 LeakyReLU,
- * 2 GELU): nn.Linear / attention products of the DINO ViT (models/dino_vit.py:110-134) on the split-bf16 conv
- * kernel -- a 1x1 convolution whose "pixels" are the M rows. */
-extern "C" int rcf_gemm_nt_f32(const float *A, int lda, const float *B, int ldb, const float *bias, float *C, int ldc,
-                               int M, int N, int K, int act, float slope, int beta, const unsigned *amax_a,
-                               const unsigned *amax_b, const void *b_pairs, unsigned *amax_out, void *stream) {
+// the GEMM view of the conv kernels' parameters -- a 1x1 convolution whose "pixels" are the M rows -- after the argument checks
+// both GEMM entry points share.  Returns 0 / RCF_EINVAL.
+int gemm_params(IgemmParams &p, const float *A, int lda, const float *B, int ldb, const float *bias, float *C, int ldc, int M,
+                int N, int K, int act, float slope, int beta) {
     if (!A || !B || !C || M <= 0 || N <= 0 || K <= 0 || K % 4 || lda % 4 || ldb % 4 || ldc % 4) return RCF_EINVAL;
     if (lda < K || ldb < K || ldc < N || !rcf_aligned16(A) || !rcf_aligned16(B) || !rcf_aligned16(C)) return RCF_EINVAL;
     if ((long)M * lda >= (1L << 29) || (long)N * ldb >= (1L << 29)) return RCF_EINVAL;      // 32-bit descriptor offsets
-    IgemmParams p{};
     p.A = A; p.Bw = B; p.bias = bias; p.Y = C;
     p.M = M; p.Ncol = N; p.K = K;
     p.Ho = M; p.Wo = 1; p.Hs = M; p.Ws = 1; p.Cs = K; p.S = 1;
@@ -2326,6 +2287,19 @@ extern "C" int rcf_gemm_nt_f32(const float *A, int lda, const float *B, int ldb,
     p.a_pitch = lda; p.a_img_stride = (long)M * lda; p.y_pitch = ldc;
     p.ldb = ldb; p.act = act; p.slope = slope; p.beta = beta;
     p.ry0 = 0; p.rx0 = 0; p.rh = M; p.rw = 1; p.rband = 0; p.rr = M;
+    return 0;
+}
+
+}  // namespace
+
+/* C[M][N] (pitch ldc) (+)= A[M][K] (pitch lda) . B[N][K]^T (pitch ldb) + bias[N], then act (0 none, 1 LeakyReLU,
+ * 2 GELU): nn.Linear / attention products of the DINO ViT (models/dino_vit.py:110-134) on the split-bf16 conv
+ * kernel. */
+extern "C" int rcf_gemm_nt_f32(const float *A, int lda, const float *B, int ldb, const float *bias, float *C, int ldc,
+                               int M, int N, int K, int act, float slope, int beta, const unsigned *amax_a,
+                               const unsigned *amax_b, const void *b_pairs, unsigned *amax_out, void *stream) {
+    IgemmParams p{};
+    if (int e = gemm_params(p, A, lda, B, ldb, bias, C, ldc, M, N, K, act, slope, beta)) return e;
     // operand ranges -> fp16-pair kernels; B already split (rcf_conv_weight_pairs_f32 with Cout = N, Cin = K, R = S = 1)
     // needs the plain layout it was made from (ldb == K)
     if (b_pairs && ldb != K) return RCF_EINVAL;
@@ -2338,19 +2312,10 @@ extern "C" int rcf_gemm_nt_f32(const float *A, int lda, const float *B, int ldb,
 extern "C" int rcf_gemm_nt_batched_f32(const float *A, int lda, long a_s0, long a_s1, const float *B, int ldb, long b_s0,
                                        long b_s1, float *C, int ldc, long c_s0, long c_s1, int batch0, int batch1, int M,
                                        int N, int K, int act, float slope, int beta, void *stream) {
-    if (!A || !B || !C || M <= 0 || N <= 0 || K <= 0 || K % 4 || lda % 4 || ldb % 4 || ldc % 4) return RCF_EINVAL;
-    if (lda < K || ldb < K || ldc < N || !rcf_aligned16(A) || !rcf_aligned16(B) || !rcf_aligned16(C)) return RCF_EINVAL;
+    IgemmParams p{};
+    if (int e = gemm_params(p, A, lda, B, ldb, nullptr, C, ldc, M, N, K, act, slope, beta)) return e;
     if (batch0 <= 0 || batch1 <= 0 || (long)batch0 * batch1 > 65535) return RCF_EINVAL;
     if ((a_s0 | a_s1 | b_s0 | b_s1 | c_s0 | c_s1) % 4) return RCF_EINVAL;
-    if ((long)M * lda >= (1L << 29) || (long)N * ldb >= (1L << 29)) return RCF_EINVAL;
-    IgemmParams p{};
-    p.A = A; p.Bw = B; p.bias = nullptr; p.Y = C;
-    p.M = M; p.Ncol = N; p.K = K;
-    p.Ho = M; p.Wo = 1; p.Hs = M; p.Ws = 1; p.Cs = K; p.S = 1;
-    p.up = 1; p.off = 0; p.step = 1; p.div = 1;
-    p.a_pitch = lda; p.a_img_stride = (long)M * lda; p.y_pitch = ldc;
-    p.ldb = ldb; p.act = act; p.slope = slope; p.beta = beta;
-    p.ry0 = 0; p.rx0 = 0; p.rh = M; p.rw = 1; p.rband = 0; p.rr = M;
     p.batch1 = batch1; p.a_bs0 = a_s0; p.a_bs1 = a_s1; p.b_bs0 = b_s0; p.b_bs1 = b_s1; p.y_bs0 = c_s0; p.y_bs1 = c_s1;
     return launch_igemm_x3(p, rcf_stream(stream), batch0 * batch1);
 }
@@ -2567,10 +2532,7 @@ extern "C" size_t rcf_conv2d_dgrad_bnsums_workspace_bytes(const rcf_conv_shape *
 }
 
 extern "C" int rcf_conv2d_dgrad_bnsums_ok(const rcf_conv_shape *s) {
-    if (check_shape(s) || !use_x3(s->flags) || s->Cout % 4) return 0;
-    const int bnw = s->Cin > 128 ? 256 : (s->Cin > 64 ? 128 : 64);
-    const void *wpt = s->w_pairs2_t ? s->w_pairs2_t : s->w_pairs_t;
-    if (s->Cin % bnw || !wpt || !s->amax_dy || !s->amax_w) return 0;
+    if (check_shape(s) || s->Cout % 4 || !dgrad_lean_ok(s)) return 0;
     if ((s->flags & RCF_CONV_DY_PLANES) && !(s->w_pairs2_t && pairs2_written(s->R * s->S * s->Cout, s->Cout))) return 0;
     return 1;
 }
@@ -2606,11 +2568,8 @@ int conv2d_dgrad_impl(const float *dy, const float *w, float *dx, const rcf_conv
     IgemmParams p{};
     p.flags = s->flags;
     if (add) {
-        // the masked addend lives in the lean epilogue of the fp16-pair kernels, like the batch-norm sums below: same conditions
-        const int bnw = s->Cin > 128 ? 256 : (s->Cin > 64 ? 128 : 64);
-        const void *wpt = s->w_pairs2_t ? s->w_pairs2_t : s->w_pairs_t;
-        if (!use_x3(s->flags) || region || beta || s->Cin % bnw || !wpt || !s->amax_dy || !s->amax_w || !add_mask || add_pitch % 4 ||
-            add_pitch < s->Cin || !rcf_aligned16(add))
+        // the masked addend lives in the lean epilogue of the fp16-pair kernels, like the batch-norm sums below
+        if (!dgrad_lean_ok(s) || region || beta || !add_mask || add_pitch % 4 || add_pitch < s->Cin || !rcf_aligned16(add))
             return RCF_EINVAL;
         p.flags |= RCF_CONV_H2P_NEVER;
         p.add_src = add; p.add_pitch = add_pitch; p.add_mask = add_mask;
@@ -2618,11 +2577,8 @@ int conv2d_dgrad_impl(const float *dy, const float *w, float *dx, const rcf_conv
     if (bn) {
         // the batch-norm sums come out of the lean epilogue of the 128-row fp16-pair kernels: whole column tiles, the whole tensor,
         // weights prepared by the caller (the workspace holds the partial sums), not the persistent kernel (its own epilogue)
-        const int bnw = s->Cin > 128 ? 256 : (s->Cin > 64 ? 128 : 64);
-        const void *wpt = s->w_pairs2_t ? s->w_pairs2_t : s->w_pairs_t;
-        if (!use_x3(s->flags) || region || s->Cin % bnw || !wpt || !s->amax_dy || !s->amax_w || !stats || !bn->x || !bn->relu_mask ||
-            !bn->mean || !bn->invstd || bn->x_pitch % 4 || bn->x_pitch < s->Cin || !rcf_aligned16(bn->x) || !rcf_aligned16(bn->mean) ||
-            !rcf_aligned16(bn->invstd))
+        if (!dgrad_lean_ok(s) || region || !stats || !bn->x || !bn->relu_mask || !bn->mean || !bn->invstd || bn->x_pitch % 4 ||
+            bn->x_pitch < s->Cin || !rcf_aligned16(bn->x) || !rcf_aligned16(bn->mean) || !rcf_aligned16(bn->invstd))
             return RCF_EINVAL;
         p.flags |= RCF_CONV_H2P_NEVER;
         p.stats = stats;
@@ -2671,12 +2627,16 @@ int conv2d_dgrad_impl(const float *dy, const float *w, float *dx, const rcf_conv
 }
 }  // namespace
 
-namespace {
-bool region_ok(const rcf_conv_region *r, int H, int W) {
-    return !r || (r->y0 >= 0 && r->x0 >= 0 && r->h > 0 && r->w > 0 && r->y0 + r->h <= H && r->x0 + r->w <= W &&
-                  r->band >= 0 && (r->band == 0 || (2 * r->band < r->h && 2 * r->band < r->w)));
+// rcf_common.h: the split-K reduction of both weight gradients (this file's and csrc/igemm_bf16.hip's)
+int rcf_splitk_reduce(const float *ws, float *dw, long n, long split_stride, int splits, int beta, void *stream) {
+    const long n4 = n / 4;
+    // small weights: one wavefront per workgroup, so that the few thousand float4 spread over all CUs
+    const int bt = n4 < (1 << 17) ? 64 : 256;
+    const int blocks = (int)((n4 + bt - 1) / bt < 4096 ? (n4 + bt - 1) / bt : 4096);
+    hipLaunchKernelGGL(splitk_reduce_kernel, dim3(blocks), dim3(bt), 0, rcf_stream(stream), ws, dw, n4, split_stride, splits, beta);
+    RCF_LAUNCH_CHECK();
+    return 0;
 }
-}  // namespace
 
 extern "C" size_t rcf_conv2d_wgrad_workspace_bytes(const rcf_conv_shape *s) {
     return rcf_conv2d_wgrad_region_workspace_bytes(s, nullptr);
@@ -2712,10 +2672,8 @@ extern "C" int rcf_conv2d_wgrad_region_f32(const float *x, const float *dy, floa
     p.Cout = s->Cout; p.Cin = s->Cin; p.R = s->R; p.S = s->S;
     p.H = s->H; p.W = s->W; p.Ho = s->Ho; p.Wo = s->Wo; p.stride = s->stride; p.pad = s->pad; p.dil = s->dil;
     p.x_pitch = s->x_pitch; p.dy_pitch = s->y_pitch;
-    p.ry0 = region ? region->y0 : 0; p.rx0 = region ? region->x0 : 0;
-    p.rh = region ? region->h : s->Ho; p.rw = region ? region->w : s->Wo;
-    p.rband = region ? region->band : 0; p.rr = region_pixels(region, s->Ho, s->Wo);
-    p.M = (long)s->N * p.rr; p.chunk = pl.chunk; p.itiles = pl.itiles; p.jtiles = pl.jtiles;
+    fill_region(p, region, s->N, s->Ho, s->Wo);
+    p.chunk = pl.chunk; p.itiles = pl.itiles; p.jtiles = pl.jtiles;
     p.split_stride = (long)s->Cout * s->R * s->S * s->Cin; p.beta = beta;
     p.amax_a = s->amax_dy; p.amax_b = s->amax_x;
     p.xcd_map = (s->flags & RCF_CONV_NO_WGRAD_XCD) ? 0 : 1;
@@ -2786,14 +2744,6 @@ extern "C" int rcf_conv2d_wgrad_region_f32(const float *x, const float *dy, floa
     else RCF_WGRAD_LAUNCH(1, 1);
 #undef RCF_WGRAD_LAUNCH
     RCF_LAUNCH_CHECK();
-    if (pl.splitk > 1) {
-        const long n4 = p.split_stride / 4;
-        // small weights: one wavefront per workgroup, so that the few thousand float4 spread over all CUs
-        const int bt = n4 < (1 << 17) ? 64 : 256;
-        const int blocks = (int)((n4 + bt - 1) / bt < 4096 ? (n4 + bt - 1) / bt : 4096);
-        hipLaunchKernelGGL(splitk_reduce_kernel, dim3(blocks), dim3(bt), 0, st, (const float *)workspace, dw, n4,
-                           p.split_stride, pl.splitk, beta);
-        RCF_LAUNCH_CHECK();
-    }
+    if (pl.splitk > 1) return rcf_splitk_reduce((const float *)workspace, dw, p.split_stride, p.split_stride, pl.splitk, beta, stream);
     return 0;
 }

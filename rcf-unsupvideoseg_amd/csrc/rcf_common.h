@@ -18,6 +18,9 @@ static inline hipStream_t rcf_stream(void *s) { return (hipStream_t)s; }
 // the batch-norm constants + running statistics + num_batches_tracked, in one launch.  scratch: 64 rows of 2C doubles.
 int rcf_sum_partials_bn(const double *partial, int chunks, int C, double *sums, double *scratch,
                         const rcf_bn_finalize *fin, void *stream);
+// igemm_conv.hip (splitk_reduce_kernel): dw[n] (+ dw when beta) = the sum of the `splits` partial weight gradients
+// ws[s * split_stride ...], added in a fixed order; n % 4 == 0, 16-byte aligned
+int rcf_splitk_reduce(const float *ws, float *dw, long n, long split_stride, int splits, int beta, void *stream);
 
 // csrc/crf_sort.hip: rocPRIM radix sort / inclusive scan for the sort-based lattice build (csrc/crf.hip)
 size_t rcf_crf_sort_tmp_bytes(size_t n);

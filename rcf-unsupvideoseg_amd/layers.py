@@ -229,6 +229,51 @@ def _param_grad(p):
     return p.grad
 
 
+def _col_tile_ok(n):
+    """n columns are whole column tiles of the conv kernels (64 | 128 | multiples of 256): what their fused epilogues need"""
+    return n in (64, 128) or n % 256 == 0
+
+
+def _stats_act(y, sums, bn):
+    """the Act of a conv output whose epilogue produced the following norm's statistics (`bn` given: finalized it)"""
+    ya = Act(y)
+    ya.bn, ya.stats = (sums, None) if bn is not None else (None, sums)
+    return ya
+
+
+def _reader_token(x):
+    """(token, first): the first reader of x in forward order is the last writer of x's gradient in the backward pass"""
+    tok, first = object(), x.first_reader is None
+    if first:
+        x.first_reader = tok
+    return tok, first
+
+
+def _wgrad_on_side_stream(dy, xw, dgrad, launch):
+    """SCHED.overlap_wgrad: the weight gradient `launch()` on the second stream.  SCHED.late_wgrad: the data gradient first,
+    alone; the weight gradient starts when it is done and so runs beside the NEXT layer's batch-norm backward (HBM-bound)
+    instead of beside this layer's data gradient (MFMA-bound like itself)"""
+    side = _side_stream(dy.device)
+    if SCHED.late_wgrad:
+        dgrad()
+    side.wait_stream(torch.cuda.current_stream(dy.device))       # dy is ready (SCHED.late_wgrad: the data gradient is done)
+    with torch.cuda.stream(side):
+        launch()
+    dy.record_stream(side)
+    xw.record_stream(side)
+
+
+def _exchange_sums2(dist, s2, r_s2, residual):
+    """SyncBN backward: all-reduce a norm's sums s2 -- with r_s2, the backward sums of the (plain) downsample norm that produced
+    `residual`, taken from the same masked gradient, in the SAME exchange: one latency-bound collective instead of two"""
+    if r_s2 is None:
+        dist.allreduce_sum(s2)
+    else:
+        r_local = r_s2.clone()               # dgamma / dbeta stay per rank
+        dist.allreduce_sum_many([s2, r_s2])
+        residual.grad_sums2 = (r_s2, r_local)
+
+
 class Conv2d(nn.Module):
     """Bias-free (or biased) square conv; weight kept in channels_last memory ([Cout][R][S][Cin]).
     `cin_pad`: the kernels need Cin % 4 == 0; 3-/2-channel inputs arrive zero-padded to 4 and the
@@ -298,6 +343,26 @@ class Conv2d(nn.Module):
         b[:self.cout].copy_(self.bias.detach())
         return b
 
+    def _bias_grad(self, dy):
+        if self.bias is None or not self.bias.requires_grad:
+            return
+        if dy.shape[3] == self.cout:
+            ops.colsum(dy, _param_grad(self.bias), beta=1)
+        else:                                                    # Cout padded: the real channels are the first ones
+            db = torch.zeros(dy.shape[3], dtype=torch.float32, device=dy.device)
+            ops.colsum(dy, db, beta=0)
+            _param_grad(self.bias).add_(db[:self.cout])
+
+    def _add_padded_wgrad(self, dwp):
+        """param.grad += the weight gradient of a padded weight copy (_packed_weight / the 8-channel stem)"""
+        g = _param_grad(self.weight)
+        if dwp.shape[1] != self.cin:
+            dw = ops.nhwc_to_nchw(dwp.permute(0, 2, 3, 1), self.cin)          # [Cout,Cin,R,S]
+            ops.copy2d(dw, dw.numel(), g, g.numel(), 1, dw.numel(), beta=1)
+        else:
+            n = g.numel()                                                   # Cout padded: prefix = the real rows
+            ops.copy2d(dwp.permute(0, 2, 3, 1), n, g.permute(0, 2, 3, 1), n, 1, n, beta=1)
+
     def _fwd_bf16_padded_cin(self, x, tape, out, stats):
         """the stem (3 input channels) on the bf16 kernels: the image arrives as bf16 NHWC zero-padded to 8 channels
         (`BF16_STEM`), the [Cout,Cin,R,S] parameter is re-packed to [Cout][R][S][8] once per weight update.  No data
@@ -310,23 +375,14 @@ class Conv2d(nn.Module):
         want = bool(stats) and SCHED.fuse_bn_stats
         bn = stats if isinstance(stats, BatchNorm2d) else None
         res = ops.conv2d_fwd_bf16(x.t, wpad, wb, None, self.stride, self.padding, self.dilation, stats=want, bn=bn if want else None)
-        if want:
-            ya = Act(res[0])
-            if bn is not None:
-                ya.bn = res[1]
-            else:
-                ya.stats = res[1]
-        else:
-            ya = Act(res)
+        ya = _stats_act(res[0], res[1], bn) if want else Act(res)
         if tape.enabled:
             def bwd():
                 dy = ya.take_grad()
                 if self.weight.requires_grad:
                     dwp = torch.empty_like(wpad)
                     ops.conv2d_wgrad_bf16(x.t, dy, wpad, dwp, self.stride, self.padding, self.dilation, beta=0)
-                    g = _param_grad(self.weight)
-                    dw = ops.nhwc_to_nchw(dwp.permute(0, 2, 3, 1), self.cin)          # [Cout,Cin,R,S]
-                    ops.copy2d(dw, dw.numel(), g, g.numel(), 1, dw.numel(), beta=1)
+                    self._add_padded_wgrad(dwp)
             tape.push(bwd)
         return ya
 
@@ -349,27 +405,15 @@ class Conv2d(nn.Module):
                 bn = stats if isinstance(stats, BatchNorm2d) else None
                 y, sums = ops.conv2d_fwd_bf16(x.t, w, self._derived("bf16", lambda: ops.weight_bf16(w)), None, self.stride,
                                               self.padding, self.dilation, stats=True, bn=bn)
-                ya = Act(y)
-                if bn is not None:
-                    ya.bn = sums
-                else:
-                    ya.stats = sums
+                ya = _stats_act(y, sums, bn)
             else:
                 ya = Act(ops.conv2d_fwd_bf16(x.t, w, self._derived("bf16", lambda: ops.weight_bf16(w)), b, self.stride,
                                              self.padding, self.dilation, out=out))
-        tok = object()
-        if x.first_reader is None:
-            x.first_reader = tok                   # first reader in forward order = last writer of x's gradient in the backward pass
+        tok, _ = _reader_token(x)
         if tape.enabled:
             def bwd():
                 dy = ya.take_grad()
-                if self.bias is not None and self.bias.requires_grad:
-                    if dy.shape[3] == self.cout:
-                        ops.colsum(dy, _param_grad(self.bias), beta=1)
-                    else:
-                        db = torch.zeros(dy.shape[3], dtype=torch.float32, device=dy.device)
-                        ops.colsum(dy, db, beta=0)
-                        _param_grad(self.bias).add_(db[:self.cout])
+                self._bias_grad(dy)
                 wk = self.weight
                 if dy.dtype not in ops.H16:
                     # fp32 gradient of an fp32 output: as bf16 with the channels zero-padded to a multiple of 8
@@ -384,9 +428,8 @@ class Conv2d(nn.Module):
                 def dgrad():
                     gx, beta = x.grad_slot()
                     wt = self._derived("bf16_t", lambda: ops.weight_bf16(wk, True)) if wk is self.weight else None
-                    tile = 64 if self.cin <= 64 else (128 if self.cin <= 128 else 256)
                     if (SCHED.fold_masked_dgrad and x.relu_out and x.first_reader is tok and wt is not None and self.stride == 1
-                            and self.cin % tile == 0 and gx.dtype in ops.H16 and x.t.dtype in ops.H16):
+                            and _col_tile_ok(self.cin) and gx.dtype in ops.H16 and x.t.dtype in ops.H16):
                         # x is the output of a folded conv + norm + ReLU and this is the LAST writer of its gradient: the mask of
                         # that ReLU and the column sums its backward needs come out of this epilogue (no pass over the gradient)
                         _, cs = ops.conv2d_dgrad_masked_bf16(dy, wk, x.t.shape, wt, x.t, gx, beta=beta, stride=self.stride,
@@ -400,21 +443,13 @@ class Conv2d(nn.Module):
                     padded = wk is not self.weight
                     dw = torch.empty_like(wk) if padded else _param_grad(self.weight)
                     if SCHED.overlap_wgrad and x.needs_grad and not padded:
-                        side = _side_stream(dy.device)
-                        if SCHED.late_wgrad:
-                            dgrad()                   # see SCHED.late_wgrad: the weight gradient beside the next batch-norm backward
-                        side.wait_stream(torch.cuda.current_stream(dy.device))
-                        with torch.cuda.stream(side):
-                            ops.conv2d_wgrad_bf16(x.t, dy, wk, dw, self.stride, self.padding, self.dilation, beta=1)
-                        dy.record_stream(side)
-                        x.t.record_stream(side)
+                        _wgrad_on_side_stream(dy, x.t, dgrad, lambda: ops.conv2d_wgrad_bf16(
+                            x.t, dy, wk, dw, self.stride, self.padding, self.dilation, beta=1))
                     else:
                         ops.conv2d_wgrad_bf16(x.t, dy, wk, dw, self.stride, self.padding, self.dilation,
                                               beta=0 if padded else 1)
-                    if padded:                                           # prefix = the real rows
-                        g = _param_grad(self.weight)
-                        n = g.numel()
-                        ops.copy2d(dw.permute(0, 2, 3, 1), n, g.permute(0, 2, 3, 1), n, 1, n, beta=1)
+                    if padded:
+                        self._add_padded_wgrad(dw)
                 if x.needs_grad and not done_dgrad[0]:
                     dgrad()
             tape.push(bwd)
@@ -433,12 +468,11 @@ class Conv2d(nn.Module):
         if x.split and not use_pl:
             raise ops._lib.RcfHipError("this activation exists as fp16 pair planes only and the conv cannot read them")
         xin = x.planes if use_pl else x.t
-        tok = object()
-        if x.first_reader is None:
-            x.first_reader = tok                   # first reader in forward order = last writer of x's gradient in the backward pass
-            # ... and as such it can take the identity branch's deferred gradient as a masked addend (checked again at launch)
+        tok, first = _reader_token(x)
+        if first:
+            # the last writer of x's gradient can take the identity branch's deferred gradient as a masked addend (checked again at launch)
             x.addend_ok = (SCHED.defer_residual and SCHED.fp16_pairs and tape.enabled and out is None and w is self.weight and
-                           (self.cin in (64, 128) or self.cin % 256 == 0))
+                           _col_tile_ok(self.cin))
         yamax = None
         if SCHED.fp16_pairs:
             own = w is self.weight                                       # padded copies are rebuilt per call: not cached
@@ -453,11 +487,7 @@ class Conv2d(nn.Module):
             bn = stats if isinstance(stats, BatchNorm2d) else None
             y, sums = ops.conv2d_fwd_stats(xin, w, self.stride, self.padding, self.dilation, amax=(ax, aw), w_pairs=wp, bn=bn,
                                            x_planes=use_pl, amax_y=yamax)
-            ya = Act(y)
-            if bn is not None:
-                ya.bn = sums
-            else:
-                ya.stats = sums
+            ya = _stats_act(y, sums, bn)
         else:
             y = ops.conv2d_fwd(xin, w, b, self.stride, self.padding, self.dilation, self.act, self.slope, out=out,
                                amax=(ax, aw), w_pairs=wp, x_planes=use_pl, amax_y=yamax)
@@ -498,18 +528,9 @@ class Conv2d(nn.Module):
                 if self.weight.requires_grad:
                     if self.cin_pad == self.cin and self.cout_pad == self.cout:
                         if SCHED.overlap_wgrad and x.needs_grad:
-                            side = _side_stream(dy.device)
-                            if SCHED.late_wgrad:
-                                # the data gradient first, alone; the weight gradient starts when it is done and so runs beside
-                                # the NEXT layer's batch-norm backward (HBM-bound) instead of beside this layer's data
-                                # gradient (MFMA-bound like itself)
-                                late_dgrad()
-                            side.wait_stream(torch.cuda.current_stream(dy.device))       # dy is ready (SCHED.late_wgrad: the data gradient is done)
-                            with torch.cuda.stream(side):
-                                ops.conv2d_wgrad(xw, dy, w, _param_grad(self.weight), self.stride, self.padding,
-                                                 self.dilation, beta=1, amax=(ax, ady), small_tile=SCHED.late_wgrad, planes=xpl)
-                            dy.record_stream(side)
-                            xw.record_stream(side)
+                            _wgrad_on_side_stream(dy, xw, late_dgrad, lambda: ops.conv2d_wgrad(
+                                xw, dy, w, _param_grad(self.weight), self.stride, self.padding, self.dilation, beta=1,
+                                amax=(ax, ady), small_tile=SCHED.late_wgrad, planes=xpl))
                         else:
                             ops.conv2d_wgrad(xw, dy, w, _param_grad(self.weight), self.stride, self.padding,
                                              self.dilation, beta=1, amax=(ax, ady), planes=xpl)
@@ -517,20 +538,8 @@ class Conv2d(nn.Module):
                         dwp = torch.empty_like(w)
                         ops.conv2d_wgrad(x.t, dy, w, dwp, self.stride, self.padding, self.dilation, beta=0,
                                          amax=(ax, ady))
-                        g = _param_grad(self.weight)
-                        if self.cin_pad != self.cin:
-                            dw = ops.nhwc_to_nchw(dwp.permute(0, 2, 3, 1), self.cin)      # [Cout,Cin,R,S]
-                            ops.copy2d(dw, dw.numel(), g, g.numel(), 1, dw.numel(), beta=1)
-                        else:
-                            n = g.numel()                                                   # prefix = real rows
-                            ops.copy2d(dwp.permute(0, 2, 3, 1), n, g.permute(0, 2, 3, 1), n, 1, n, beta=1)
-                if self.bias is not None and self.bias.requires_grad:
-                    if self.cout_pad == self.cout:
-                        ops.colsum(dy, _param_grad(self.bias), beta=1)
-                    else:
-                        db = torch.zeros(self.cout_pad, dtype=torch.float32, device=dy.device)
-                        ops.colsum(dy, db, beta=0)
-                        _param_grad(self.bias).add_(db[:self.cout])
+                        self._add_padded_wgrad(dwp)
+                self._bias_grad(dy)
                 if x.needs_grad and not done_dgrad[0]:
                     late_dgrad()
             tape.push(bwd)
@@ -647,6 +656,10 @@ class BatchNorm2d(nn.Module):
                 # (decided with the FORWARD pass's setting: a conv whose input exists as planes only cannot take an fp32 gradient,
                 # whatever the schedule object says by the time the backward pass runs)
                 relu_b, rmask_b, y_b = relu, rmask, y
+
+                def plane_grad(xa, g):                # does xa's producer take its output gradient (g: what it is made from) as planes?
+                    return (xa.accepts_plane_grad and planes_at_fwd and xa.t.dtype == torch.float32 and xa.amax is not None
+                            and g.dtype == torch.float32)
                 pend = None
                 if ya.res_norm is not None and ya.pending_add is not None and ya.grad is None:
                     # lazy downsample norm: the join left (its output gradient, its sign bits) instead of writing this norm's
@@ -655,14 +668,12 @@ class BatchNorm2d(nn.Module):
                 if pend is not None:
                     dy, rmask_b = pend
                     relu_b, y_b = True, None
-                    dpl = (x.accepts_plane_grad and planes_at_fwd and xt.dtype == torch.float32 and x.amax is not None
-                           and dy.dtype == torch.float32)
+                    dpl = plane_grad(x, dy)
                     ady, ya.grad_amax = ya.grad_amax, None       # the join's: the mask only lowers the range
                     if dpl and ady is None:
                         ady = ops.absmax(dy)
                 else:
-                    dpl = (x.accepts_plane_grad and planes_at_fwd and xt.dtype == torch.float32 and x.amax is not None
-                           and (not relu or rmask is not None) and ya.grad is not None and ya.grad.dtype == torch.float32)
+                    dpl = (not relu or rmask is not None) and ya.grad is not None and plane_grad(x, ya.grad)
                     ady = ya.take_grad_range() if dpl else None
                     dy = ya.take_grad()
                 s2, ya.grad_sums2 = ya.grad_sums2, None          # from the epilogue of the data gradient that wrote dy last
@@ -674,9 +685,7 @@ class BatchNorm2d(nn.Module):
                     # ONE reduction and ONE apply pass over dy and the sign bits for both (rcf_bn_bwd_reduce2_mp / _apply2_mp)
                     bn_d, x_d, count_d = residual.res_ctx
                     mean_d, invstd_d = residual.res_norm[0], residual.res_norm[1]
-                    dpl_d = (x_d.accepts_plane_grad and planes_at_fwd and x_d.t.dtype == torch.float32 and x_d.amax is not None
-                             and dy.dtype == torch.float32)
-                    if dpl_d == dpl and count_d == count and x_d.t.is_contiguous() and xt.is_contiguous():
+                    if plane_grad(x_d, dy) == dpl and count_d == count and x_d.t.is_contiguous() and xt.is_contiguous():
                         C = xt.shape[3]
                         sums4 = ops.bn_bwd_reduce2(dy, xt, x_d.t, mean, invstd, mean_d, invstd_d, rmask)
                         local4 = None
@@ -708,15 +717,8 @@ class BatchNorm2d(nn.Module):
                         s2 = ops.bn_bwd_reduce(dy, xt, y_b, mean, invstd, relu_b, chan_scale=chan_scale, relu_mask=rmask_b)
                     if dist is not None and dist.on:
                         s2_local = s2.clone()            # dgamma/dbeta stay per-rank; the gradient all-reduce adds them
-                        r_s2 = _residual_norm_sums(residual, dy, y_b, relu_b, rmask_b, chan_scale)
-                        if r_s2 is not None:
-                            # a stage's first block: the downsample norm's backward sums depend on this join's masked output
-                            # gradient only -- one exchange for both norms instead of two latency-bound ones
-                            r_local = r_s2.clone()
-                            dist.allreduce_sum_many([s2, r_s2])
-                            residual.grad_sums2 = (r_s2, r_local)
-                        else:
-                            dist.allreduce_sum(s2)
+                        # a stage's first block: the downsample norm's backward sums depend on this join's masked output gradient only
+                        _exchange_sums2(dist, s2, _residual_norm_sums(residual, dy, y_b, relu_b, rmask_b, chan_scale), residual)
                 dres, rbeta = (None, 0)
                 if residual is not None and residual.needs_grad:
                     if (residual.res_norm is not None and relu and rmask is not None and chan_scale is None and residual.grad is None
@@ -750,7 +752,7 @@ def fold_ok(conv, bn, x, residual=None):
     t = x.t
     return (SCHED.fold_bn and t.dtype in ops.H16 and conv.k == 1 and conv.stride == 1 and conv.padding == 0 and conv.bias is None
             and not conv.act and bn.training and conv.cin % 64 == 0 and conv.cin <= SCHED.fold_max_k
-            and (conv.cout in (64, 128) or conv.cout % 256 == 0) and ops.relu_mask_colsum_ok(conv.cout)
+            and _col_tile_ok(conv.cout) and ops.relu_mask_colsum_ok(conv.cout)
             and t.is_contiguous() and bn.num_features == conv.cout
             and (residual is None or (residual.t.dtype == t.dtype and tuple(residual.t.shape[:3]) == tuple(t.shape[:3])
                                       and residual.t.shape[3] == conv.cout)))
@@ -824,12 +826,7 @@ def conv_bn_fold(conv, bn, x, tape, relu, residual=None, dist=None):
                     xr, mean_r, invstd_r = residual.bn_in
                     if xr.dtype == g.dtype:
                         r_s2 = ops.bn_bwd_reduce(g, xr, None, mean_r, invstd_r, False)
-                if r_s2 is not None:
-                    r_local = r_s2.clone()
-                    dist.allreduce_sum_many([sums2, r_s2])
-                    residual.grad_sums2 = (r_s2, r_local)
-                else:
-                    dist.allreduce_sum(sums2)
+                _exchange_sums2(dist, sums2, r_s2, residual)
             negT, c0 = ops.fold_bwd_prepare(
                 G, P, A1, w, sums2, s2_local, count, mean, invstd, bn.weight, _param_grad(w) if w.requires_grad else None,
                 _param_grad(bn.weight) if bn.weight.requires_grad else None, _param_grad(bn.bias) if bn.bias.requires_grad else None)

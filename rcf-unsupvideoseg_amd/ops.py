@@ -282,25 +282,21 @@ def weight_checksum(w):
     return (float(d.abs().max()), float(d.double().sum()))
 
 
+def weight_pairs(w, amax_w, transpose=False):
+    """the fp16-pair split of a conv weight (channels_last [Cout,Cin,R,S]) for the forward launches that read it: a uint8
+    buffer holding the two fp16 planes in both reading orders (rcf_conv_weight_pairs2_f32: the 128 x 256 kernel's and the
+    persistent LDS-DMA kernel's).  transpose: the planes the data gradient contracts against (weight_pairs_t)"""
+    _need_cuda(w)
+    Cout, Cin, R, S = w.shape
+    planes = torch.empty(_lib.load().rcf_conv_weight_pairs2_bytes(Cout, Cin, R, S, int(transpose)), dtype=torch.uint8, device=w.device)
+    call("rcf_conv_weight_pairs2_f32", _p(weight_rsck(w)), Cout, Cin, R, S, int(transpose), _p(amax_w), _p(planes), CONV_FLAGS, _stream())
+    return planes
+
+
 def weight_pairs_t(w, amax_w):
     """the transposed fp16-pair planes the data gradient contracts against (once per weight update, not per launch), in
     both reading orders (rcf_conv_weight_pairs2_f32, transpose = 1): conv2d_dgrad(w_pairs_t=...)"""
-    _need_cuda(w)
-    Cout, Cin, R, S = w.shape
-    planes = torch.empty(_lib.load().rcf_conv_weight_pairs2_bytes(Cout, Cin, R, S, 1), dtype=torch.uint8, device=w.device)
-    call("rcf_conv_weight_pairs2_f32", _p(weight_rsck(w)), Cout, Cin, R, S, 1, _p(amax_w), _p(planes), CONV_FLAGS, _stream())
-    return planes
-
-
-def weight_pairs(w, amax_w):
-    """the fp16-pair split of a conv weight (channels_last [Cout,Cin,R,S]) for the forward launches that read it: a uint8
-    buffer holding the two fp16 planes in both reading orders (rcf_conv_weight_pairs2_f32: the 128 x 256 kernel's and the
-    persistent LDS-DMA kernel's)"""
-    _need_cuda(w)
-    Cout, Cin, R, S = w.shape
-    planes = torch.empty(_lib.load().rcf_conv_weight_pairs2_bytes(Cout, Cin, R, S, 0), dtype=torch.uint8, device=w.device)
-    call("rcf_conv_weight_pairs2_f32", _p(weight_rsck(w)), Cout, Cin, R, S, 0, _p(amax_w), _p(planes), CONV_FLAGS, _stream())
-    return planes
+    return weight_pairs(w, amax_w, True)
 
 
 def set_conv_flags(flags):
@@ -317,11 +313,50 @@ if os.environ.get("RCF_CONV_FLAGS"):               # e.g. RCF_CONV_FLAGS=0x8 kee
     CONV_FLAGS = int(os.environ["RCF_CONV_FLAGS"], 0)
 
 
-def _relabel_conv(s, region, dgrad, family, h2p_family):
-    """profiling only: a forward / data-gradient launch that takes the persistent kernel is filed under its own family
-    (rcf_conv_kernel_of: a pure function of the launch's arguments)"""
-    if _lib.load().rcf_conv_kernel_of(byref(s), region, int(dgrad)) == 2:
-        PROFILE.relabel_last(family, h2p_family)
+# The profiling family (bench.py FAMILIES_F32 / FAMILIES_BF16) of a conv launch, one rule per direction.  kind: "f32" (fp32
+# tensors), "planes" (fp16 pair planes in), "h16" (16-bit tensors); the fp32 weight gradient also "h2" (operand ranges given).
+def _fwd_family(s, kind):
+    wide = s.Cout > 128              # forward launches of the 128x256-tile kernel instance / of the narrower tiles
+    if kind == "h16":
+        return "conv_bf16_fwd" if wide else "conv_bf16_fwd_narrow"
+    return ("conv_h2d_fwd" if wide else "conv_h2d_fwd_narrow") if kind == "planes" else "conv_x3_128x256" if wide else "conv_fwd_narrow"
+
+
+def _dgrad_family(s, kind):
+    wide = s.Cin > 128 and s.stride == 1
+    if kind == "h16":
+        return "conv_bf16_dgrad_wide" if wide else "conv_bf16_dgrad_other"
+    return ("conv_h2d_dgrad" if wide else "conv_h2d_dgrad_narrow") if kind == "planes" else "conv_dgrad_wide" if wide else "conv_dgrad_other"
+
+
+def _wgrad_family(s, kind, region):
+    ktot = s.R * s.S * s.Cin                       # plan_wgrad (csrc/igemm_conv.hip, csrc/igemm_bf16.hip): the 128 x 256 tile
+    if kind == "h16":
+        return "conv_bf16_wgrad4" if (region is None and s.Cout >= 64 and ktot >= 256) else "conv_bf16_wgrad_other"
+    if kind == "planes":
+        return "conv_wgrad_h2d" if ktot >= 256 else "conv_wgrad_h2d_narrow"
+    return "conv_wgrad_h2t4" if (kind == "h2" and s.Cin % 64 == 0 and ktot >= 256 and s.Cout >= 64) else "conv_wgrad_other"
+
+
+def _profile_conv(s, direction, kind, region=None, suffix=""):
+    """Opens the profiling bracket of one conv launch (everything its wrapper issues until `_profile_end`); direction: "fwd",
+    "dgrad" or "wgrad".  Wrappers call it only when PROFILE.which is not None: one attribute test while profiling is off.
+    Returns (closing event, family), or None when the launch's family is not being recorded."""
+    if direction == "wgrad":
+        family = _wgrad_family(s, kind, region)
+    else:
+        family = _dgrad_family(s, kind) if direction == "dgrad" else _fwd_family(s, kind)
+    px = _region_pixels(region, s.H, s.W) if direction == "dgrad" else _region_pixels(region, s.Ho, s.Wo)
+    end = PROFILE.bracket(family, 2.0 * s.N * px * s.Cout * s.R * s.S * s.Cin, _shape_tag(s, region) + suffix)
+    return None if end is None else (end, family)
+
+
+def _profile_end(rec, relabel=None):
+    """closes the bracket.  relabel = (s, region, dgrad) of a forward / data-gradient launch that may take the persistent kernel
+    (rcf_conv_kernel_of: a pure function of the launch's arguments): it is then filed under that kernel's own family"""
+    rec[0].record()
+    if relabel is not None and _lib.load().rcf_conv_kernel_of(byref(relabel[0]), _region(relabel[1]), relabel[2]) == 2:
+        PROFILE.relabel_last(rec[1], "conv_h2p_dgrad" if relabel[2] else "conv_h2p_fwd")
 
 
 def fused_stats_available():
@@ -349,31 +384,6 @@ def _region(region):
     return byref(_lib.ConvRegion(*(r + [0] * (5 - len(r)))))
 
 
-def conv2d_fwd(x, w, bias=None, stride=1, pad=0, dil=1, act=0, slope=0.0, out=None, beta=0, region=None, amax=None,
-               w_pairs=None, x_planes=False, amax_y=None):
-    """region = (y0, x0, h, w) in output coordinates: only those pixels of `out` are written.
-    amax = (amax_x, amax_w): operand ranges (absmax) -> fp16-pair kernels; w_pairs: weight_pairs(w, amax_w).
-    x_planes: `x` (an fp32-typed tensor of the activation's shape) holds fp16 pair planes (RCF_CONV_X_PLANES: bn_apply's
-    `planes`); amax_y: new_amax() slot that receives the range of the output"""
-    _need_cuda(x, w)
-    s = _conv_shape(x.shape, pitch_of(x), w, stride, pad, dil, amax=None if amax is None else (amax[0], amax[1], None),
-                    w_pairs=w_pairs, flags=_lib.CONV_X_PLANES if x_planes else 0, amax_y=amax_y, nt_cols=w.shape[0])
-    if out is None:
-        out = torch.empty((s.N, s.Ho, s.Wo, s.Cout), dtype=torch.float32, device=x.device)
-    s.y_pitch = pitch_of(out)
-    end = None
-    if PROFILE.which is not None:       # forward launches of the 128x256-tile kernel instance / of the narrower tiles
-        end = PROFILE.bracket(("conv_h2d_fwd" if s.Cout > 128 else "conv_h2d_fwd_narrow") if x_planes else "conv_x3_128x256" if s.Cout > 128 else "conv_fwd_narrow",
-                              2.0 * s.N * _region_pixels(region, s.Ho, s.Wo) * s.Cout * s.R * s.S * s.Cin, _shape_tag(s, region))
-    call("rcf_conv2d_fwd_region_f32", _p(x), _p(weight_rsck(w)), _p(bias), _p(out), byref(s), _region(region), act,
-         slope, beta, _stream())
-    if end is not None:
-        end.record()
-        if not x_planes:
-            _relabel_conv(s, _region(region), 0, "conv_x3_128x256" if s.Cout > 128 else "conv_fwd_narrow", "conv_h2p_fwd")
-    return out
-
-
 def _bn_fin(bn, count, device):
     """(struct rcf_bn_finalize, mean, invstd) for a training-mode batch norm whose statistics the next launch produces:
     its final reduction also writes the normalisation constants, the running statistics and num_batches_tracked"""
@@ -385,23 +395,23 @@ def _bn_fin(bn, count, device):
     return fin, mean, invstd
 
 
-def conv2d_fwd_stats(x, w, stride=1, pad=0, dil=1, amax=None, w_pairs=None, bn=None, x_planes=False, amax_y=None):
-    """conv (no bias) whose epilogue also yields the batch-norm statistics of the output: (y, fp64 [2*Cout] sums); with
-    `bn` (a training-mode BatchNorm2d whose statistics are local) the same reduction finalizes it: (y, (mean, invstd, count)).
-    x_planes / amax_y: as conv2d_fwd"""
+def _conv2d_fwd(x, w, bias, stride, pad, dil, act, slope, out, beta, region, amax, w_pairs, x_planes, amax_y, stats=False, bn=None):
+    """conv2d_fwd, and with `stats` conv2d_fwd_stats"""
     _need_cuda(x, w)
     s = _conv_shape(x.shape, pitch_of(x), w, stride, pad, dil, amax=None if amax is None else (amax[0], amax[1], None),
                     w_pairs=w_pairs, flags=_lib.CONV_X_PLANES if x_planes else 0, amax_y=amax_y, nt_cols=w.shape[0])
-    out = torch.empty((s.N, s.Ho, s.Wo, s.Cout), dtype=torch.float32, device=x.device)
+    if out is None:
+        out = torch.empty((s.N, s.Ho, s.Wo, s.Cout), dtype=torch.float32, device=x.device)
     s.y_pitch = pitch_of(out)
-    sums = torch.empty(2 * s.Cout, dtype=torch.float64, device=x.device)
-    need = _lib.load().rcf_conv2d_fwd_stats_workspace_bytes(byref(s))
-    ws = workspace(need, x.device)
-    end = None
-    if PROFILE.which is not None:
-        end = PROFILE.bracket(("conv_h2d_fwd" if s.Cout > 128 else "conv_h2d_fwd_narrow") if x_planes else "conv_x3_128x256" if s.Cout > 128 else "conv_fwd_narrow",
-                              2.0 * s.N * s.Ho * s.Wo * s.Cout * s.R * s.S * s.Cin, _shape_tag(s))
-    if bn is not None:
+    if stats:
+        sums = torch.empty(2 * s.Cout, dtype=torch.float64, device=x.device)
+        need = _lib.load().rcf_conv2d_fwd_stats_workspace_bytes(byref(s))
+        ws = workspace(need, x.device)
+    end = _profile_conv(s, "fwd", "planes" if x_planes else "f32", region) if PROFILE.which is not None else None
+    if not stats:
+        call("rcf_conv2d_fwd_region_f32", _p(x), _p(weight_rsck(w)), _p(bias), _p(out), byref(s), _region(region), act,
+             slope, beta, _stream())
+    elif bn is not None:
         count = s.N * s.Ho * s.Wo
         fin, mean, invstd = _bn_fin(bn, count, x.device)
         call("rcf_conv2d_fwd_bnstats_f32", _p(x), _p(weight_rsck(w)), _p(out), byref(s), None, byref(fin), _p(ws), need, _stream())
@@ -409,10 +419,24 @@ def conv2d_fwd_stats(x, w, stride=1, pad=0, dil=1, amax=None, w_pairs=None, bn=N
     else:
         call("rcf_conv2d_fwd_stats_f32", _p(x), _p(weight_rsck(w)), _p(out), byref(s), _p(sums), _p(ws), need, _stream())
     if end is not None:
-        end.record()
-        if not x_planes:
-            _relabel_conv(s, None, 0, "conv_x3_128x256" if s.Cout > 128 else "conv_fwd_narrow", "conv_h2p_fwd")
-    return out, sums
+        _profile_end(end, None if x_planes else (s, region, 0))
+    return (out, sums) if stats else out
+
+
+def conv2d_fwd(x, w, bias=None, stride=1, pad=0, dil=1, act=0, slope=0.0, out=None, beta=0, region=None, amax=None,
+               w_pairs=None, x_planes=False, amax_y=None):
+    """region = (y0, x0, h, w) in output coordinates: only those pixels of `out` are written.
+    amax = (amax_x, amax_w): operand ranges (absmax) -> fp16-pair kernels; w_pairs: weight_pairs(w, amax_w).
+    x_planes: `x` (an fp32-typed tensor of the activation's shape) holds fp16 pair planes (RCF_CONV_X_PLANES: bn_apply's
+    `planes`); amax_y: new_amax() slot that receives the range of the output"""
+    return _conv2d_fwd(x, w, bias, stride, pad, dil, act, slope, out, beta, region, amax, w_pairs, x_planes, amax_y)
+
+
+def conv2d_fwd_stats(x, w, stride=1, pad=0, dil=1, amax=None, w_pairs=None, bn=None, x_planes=False, amax_y=None):
+    """conv (no bias) whose epilogue also yields the batch-norm statistics of the output: (y, fp64 [2*Cout] sums); with
+    `bn` (a training-mode BatchNorm2d whose statistics are local) the same reduction finalizes it: (y, (mean, invstd, count)).
+    x_planes / amax_y: as conv2d_fwd"""
+    return _conv2d_fwd(x, w, None, stride, pad, dil, 0, 0.0, None, 0, None, amax, w_pairs, x_planes, amax_y, True, bn)
 
 
 def conv2d_dgrad(dy, w, xshape, stride=1, pad=0, dil=1, out=None, beta=0, region=None, amax=None, w_pairs_t=None,
@@ -443,11 +467,7 @@ def conv2d_dgrad(dy, w, xshape, stride=1, pad=0, dil=1, out=None, beta=0, region
     if fuse:
         need = _lib.load().rcf_conv2d_dgrad_bnsums_workspace_bytes(byref(s))
     ws = workspace(need, dy.device) if need else None
-    end = None
-    if PROFILE.which is not None:
-        end = PROFILE.bracket(("conv_h2d_dgrad" if (s.Cin > 128 and stride == 1) else "conv_h2d_dgrad_narrow") if dy_planes else
-                              "conv_dgrad_wide" if (s.Cin > 128 and stride == 1) else "conv_dgrad_other",
-                              2.0 * s.N * _region_pixels(region, s.H, s.W) * s.Cin * s.R * s.S * s.Cout, _shape_tag(s, region))
+    end = _profile_conv(s, "dgrad", "planes" if dy_planes else "f32", region) if PROFILE.which is not None else None
     sums2 = None
     if fuse or addend is not None:
         bn = None
@@ -462,9 +482,7 @@ def conv2d_dgrad(dy, w, xshape, stride=1, pad=0, dil=1, out=None, beta=0, region
         call("rcf_conv2d_dgrad_region_f32", _p(dy), _p(weight_rsck(w)), _p(out), byref(s), _region(region), beta, _p(ws),
              need, _stream())
     if end is not None:
-        end.record()
-        if not dy_planes and not fuse and addend is None:
-            _relabel_conv(s, _region(region), 1, "conv_dgrad_wide" if (s.Cin > 128 and stride == 1) else "conv_dgrad_other", "conv_h2p_dgrad")
+        _profile_end(end, (s, region, 1) if (not dy_planes and not fuse and addend is None) else None)
     return (out, sums2) if bn_bwd is not None else out
 
 
@@ -500,15 +518,10 @@ def conv2d_wgrad(x, dy, w_like, dw, stride=1, pad=0, dil=1, beta=1, region=None,
     reg = _region(region)
     need = _lib.load().rcf_conv2d_wgrad_region_workspace_bytes(byref(s), reg)
     ws = workspace(need, x.device) if need else None
-    end = None
-    if PROFILE.which is not None:
-        ktot = s.R * s.S * s.Cin                                   # plan_wgrad (csrc/igemm_conv.hip): the 128 x 256 fp16-pair tile
-        wide = amax is not None and s.Cin % 64 == 0 and ktot >= 256 and s.Cout >= 64
-        end = PROFILE.bracket(("conv_wgrad_h2d" if ktot >= 256 else "conv_wgrad_h2d_narrow") if planes else ("conv_wgrad_h2t4" if wide else "conv_wgrad_other"),
-                              2.0 * s.N * _region_pixels(region, s.Ho, s.Wo) * s.Cout * s.R * s.S * s.Cin, _shape_tag(s, region))
+    end = _profile_conv(s, "wgrad", "planes" if planes else ("f32" if amax is None else "h2"), region) if PROFILE.which is not None else None
     call("rcf_conv2d_wgrad_region_f32", _p(x), _p(dy), _p(weight_rsck(dw)), byref(s), reg, beta, _p(ws), need, _stream())
     if end is not None:
-        end.record()
+        _profile_end(end)
     return dw
 
 
@@ -542,10 +555,7 @@ def conv2d_fwd_bf16(x, w, w_bf16=None, bias=None, stride=1, pad=0, dil=1, act=0,
         sums = torch.empty(2 * s.Cout, dtype=torch.float64, device=x.device)
         need = _lib.load().rcf_conv2d_fwd_stats_bf16_workspace_bytes(byref(s))
         ws = workspace(need, x.device)
-    end = None
-    if PROFILE.which is not None:
-        end = PROFILE.bracket("conv_bf16_fwd" if s.Cout > 128 else "conv_bf16_fwd_narrow",
-                              2.0 * s.N * _region_pixels(region, s.Ho, s.Wo) * s.Cout * s.R * s.S * s.Cin, _shape_tag(s, region))
+    end = _profile_conv(s, "fwd", "h16", region) if PROFILE.which is not None else None
     if stats and bn is not None:                     # the statistics reduction also finalizes the batch norm
         count = s.N * s.Ho * s.Wo
         fin, mean, invstd = _bn_fin(bn, count, x.device)
@@ -556,7 +566,7 @@ def conv2d_fwd_bf16(x, w, w_bf16=None, bias=None, stride=1, pad=0, dil=1, act=0,
         call("rcf_conv2d_fwd_bf16", _p(x), _p(w_bf16), _p(bias), _p(out), _dt(out), byref(s), _region(region), act, slope, beta,
              _p(sums), _p(ws), need, _stream())
     if end is not None:
-        end.record()
+        _profile_end(end)
     return (out, sums) if stats else out
 
 
@@ -571,14 +581,11 @@ def conv2d_dgrad_bf16(dy, w, xshape, stride=1, pad=0, dil=1, out=None, beta=0, r
     assert tuple(dy.shape) == (s.N, s.Ho, s.Wo, s.Cout)
     need = 0 if w_t_bf16 is not None else _lib.load().rcf_conv2d_dgrad_bf16_workspace_bytes(byref(s))
     ws = workspace(need, dy.device) if need else None
-    end = None
-    if PROFILE.which is not None:
-        end = PROFILE.bracket("conv_bf16_dgrad_wide" if (s.Cin > 128 and stride == 1) else "conv_bf16_dgrad_other",
-                              2.0 * s.N * _region_pixels(region, s.H, s.W) * s.Cin * s.R * s.S * s.Cout, _shape_tag(s, region))
+    end = _profile_conv(s, "dgrad", "h16", region) if PROFILE.which is not None else None
     call("rcf_conv2d_dgrad_bf16", _p(dy), _p(weight_rsck(w)), _p(out), byref(s), _region(region), beta, _p(ws), need,
          _stream())
     if end is not None:
-        end.record()
+        _profile_end(end)
     return out
 
 
@@ -590,14 +597,10 @@ def conv2d_wgrad_bf16(x, dy, w_like, dw, stride=1, pad=0, dil=1, beta=1, region=
     reg = _region(region)
     need = _lib.load().rcf_conv2d_wgrad_bf16_workspace_bytes(byref(s), reg)
     ws = workspace(need, x.device) if need else None
-    end = None
-    if PROFILE.which is not None:
-        wide = region is None and s.Cout >= 64 and s.R * s.S * s.Cin >= 256                     # plan_wgrad (csrc/igemm_bf16.hip)
-        end = PROFILE.bracket("conv_bf16_wgrad4" if wide else "conv_bf16_wgrad_other",
-                              2.0 * s.N * _region_pixels(region, s.Ho, s.Wo) * s.Cout * s.R * s.S * s.Cin, _shape_tag(s, region))
+    end = _profile_conv(s, "wgrad", "h16", region) if PROFILE.which is not None else None
     call("rcf_conv2d_wgrad_bf16", _p(x), _p(dy), _p(weight_rsck(dw)), byref(s), reg, beta, _p(ws), need, _stream())
     if end is not None:
-        end.record()
+        _profile_end(end)
     return dw
 
 
@@ -656,17 +659,14 @@ def conv2d_fwd_affine_bf16(x, w, w_bf16, scale, shift, residual=None, relu=True,
     s.y_pitch = pitch_of(out)
     if residual is not None:
         assert tuple(residual.shape) == tuple(out.shape)
-    end = None
-    if PROFILE.which is not None:
-        end = PROFILE.bracket("conv_bf16_fwd" if s.Cout > 128 else "conv_bf16_fwd_narrow",
-                              2.0 * s.N * s.Ho * s.Wo * s.Cout * s.R * s.S * s.Cin, _shape_tag(s) + " +bn")
+    end = _profile_conv(s, "fwd", "h16", None, " +bn") if PROFILE.which is not None else None
     bits = None
     if want_bits and relu:
         bits = torch.empty(_lib.load().rcf_conv_relu_bits_bytes(s.N * s.Ho * s.Wo, s.Cout), dtype=torch.uint8, device=x.device)
     call("rcf_conv2d_fwd_affine_bf16", _p(x), _p(w_bf16), _p(scale), _p(shift), _p(residual),
          pitch_of(residual) if residual is not None else 0, int(relu), _p(out), _p(bits), byref(s), _stream())
     if end is not None:
-        end.record()
+        _profile_end(end)
     return (out, bits) if want_bits else out
 
 
@@ -707,14 +707,11 @@ def conv2d_dgrad_masked_bf16(dy, w, xshape, w_t_bf16, mask_src, out, beta=0, str
         cs = torch.empty(2 * s.Cin, dtype=torch.float64, device=dy.device)
         need = _lib.load().rcf_conv2d_dgrad_masked_bf16_workspace_bytes(byref(s))
         ws = workspace(need, dy.device)
-    end = None
-    if PROFILE.which is not None:
-        end = PROFILE.bracket("conv_bf16_dgrad_wide" if s.Cin > 128 else "conv_bf16_dgrad_other",
-                              2.0 * s.N * s.H * s.W * s.Cin * s.R * s.S * s.Cout, _shape_tag(s) + " +mask")
+    end = _profile_conv(s, "dgrad", "h16", None, " +mask") if PROFILE.which is not None else None
     call("rcf_conv2d_dgrad_masked_bf16", _p(dy), _p(w_t_bf16), _p(out), byref(s), int(beta), _p(mask_src),
          pitch_of(mask_src) if mask_src is not None else 0, _p(mask_bits), _p(cs), _p(ws), need, _stream())
     if end is not None:
-        end.record()
+        _profile_end(end)
     return out, cs
 
 
