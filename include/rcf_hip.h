@@ -755,6 +755,15 @@ int rcf_affinity_threshold_f32(float *gram, long pitch, int n, float tau, float 
 int rcf_ncut_value_grad_f32(const float *affinity, long pitch, int n, const float *x, double *u, double *rowsum,
                             int compute_rowsum, float *grad, float *value_out, void *stream);
 int rcf_clamp01_f32(float *x, int n, void *stream);
+/* MAA (tools/SemanticConstraintsAndMAA/maa.py:19-36): the soft-NCut terms of M masks per frame in ONE pass over the RAW Gram
+ * matrices gram[frames][n][pitch], which are only read -- a_ij = (gram_ij > tau ? 1 : eps) is formed in registers and no
+ * symmetry is assumed.  masks[frames][M][n], 1 <= M <= 8; out[frames][M][4] = {ncut, cut, assocA, assocB} (fp64; IEEE
+ * semantics: an all-zero mask gives NaN).  pitch >= n, pitch % 4 == 0, gram 16-byte aligned.  Per-workgroup fp64 partials go
+ * to `workspace` and are added in a fixed order by a second launch: no atomics, bit-identical from run to run, and a frame's
+ * result does not depend on `frames` or on its position.  The grid is sized from the device's compute-unit count. */
+size_t rcf_ncut_values_workspace_bytes(int frames, int n, int M);
+int rcf_ncut_values_f32(const float *gram, long pitch, int n, int frames, float tau, float eps, const float *masks, int M,
+                        double *out, void *workspace, size_t workspace_bytes, void *stream);
 
 #ifdef __cplusplus
 }

@@ -113,6 +113,8 @@ PROTOS = {
     "rcf_affinity_threshold_f32": (c_int, [P, c_long, c_int, c_float, c_float, P]),
     "rcf_ncut_value_grad_f32": (c_int, [P, c_long, c_int, P, P, P, c_int, P, P, P]),
     "rcf_clamp01_f32": (c_int, [P, c_int, P]),
+    "rcf_ncut_values_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "rcf_ncut_values_f32": (c_int, [P, c_long, c_int, c_int, c_float, c_float, P, c_int, P, P, c_size_t, P]),
     "rcf_split_rect_f32": (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P]),
     "rcf_absmax_f32": (c_int, [P, c_long, c_int, c_int, P, P]),
     "rcf_conv_weight_pairs_f32": (c_int, [P, c_int, c_int, c_int, c_int, P, P, c_uint, P]),

@@ -225,6 +225,146 @@ __global__ void __launch_bounds__(256) ncut_value_grad_kernel(const float *__res
     }
 }
 
+// ---- soft-NCut terms of M masks in ONE pass over the raw Gram matrix (rcf_ncut_values_f32) ------------------------------
+// With a_ij = (G_ij > tau ? 1 : eps), u_i = sum_j a_ij x_j, s_i = sum_j a_ij (maa.py:19-36):
+//     assocA = sum_i u_i,   cut = sum_i (1 - x_i) u_i,   assocB = sum_i (s_i - u_i),   NCut = cut/assocA + cut/assocB.
+// All three are sums over the ELEMENTS (i, j) of terms a_ij x_j, (1 - x_i) a_ij x_j and a_ij (1 - x_j), so no row of G has to
+// be owned by one workgroup and nothing is assumed about symmetry.  The n x n matrix is cut into tiles of
+// (rows_per_tile rows) x (panel of <= 256 float4 columns); a workgroup takes one tile, thread t the four columns of quad
+// panel * pw + t for every row of the tile.
+// Where x lives: in REGISTERS, not LDS.  A thread's columns are fixed for the whole tile, so its 4 x M mask values are loaded
+// once (as fp64: no conversion in the loop) and the row's M values x_i are uniform across the workgroup (scalar loads).  Staging
+// [M][n] in LDS (103 KB at M = 4, n = 6420) would allow one workgroup per CU and cost M ds_read_b128 per 16 bytes of G; the
+// register form needs no LDS, runs 3-4 workgroups per CU and reads G with one 16-byte load per thread and row.
+// The threshold is applied in registers; G is only read.  fp64 accumulation; per-workgroup partials [3][M] go to the
+// workspace and ncut_finish_kernel adds them in a fixed order: no atomics, the same bits on every run, and a frame's result
+// depends neither on the number of frames nor on its position (grid.y = frame, the tiling depends on n alone).
+constexpr int NCUT_MAXM = 8;
+struct ncut_tiling { int nq, panels, pw, rows_per_tile, chunks; };
+
+template <int M>
+__device__ __forceinline__ void ncut_row(const f32x4 g, const float (&tau_e)[4], const double (&lo_e)[4],
+                                         const double (&xd)[M][4], const float *__restrict__ xrow, long xstride,
+                                         double (&accA)[M], double (&accC)[M], double (&accB)[M]) {
+    double a[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) a[e] = g[e] > tau_e[e] ? 1.0 : lo_e[e];
+    const double rs = (a[0] + a[1]) + (a[2] + a[3]);
+#pragma unroll
+    for (int m = 0; m < M; ++m) {
+        double r = a[0] * xd[m][0];
+        r = fma(a[1], xd[m][1], r);
+        r = fma(a[2], xd[m][2], r);
+        r = fma(a[3], xd[m][3], r);
+        accA[m] += r;
+        accC[m] = fma(1.0 - (double)xrow[m * xstride], r, accC[m]);
+        accB[m] += rs - r;
+    }
+}
+
+template <int M>
+__global__ void __launch_bounds__(256) ncut_values_kernel(const float *__restrict__ gram, long pitch, int n, float tau,
+                                                          float eps, const float *__restrict__ masks, ncut_tiling tl,
+                                                          double *__restrict__ partial) {
+    __shared__ double red[4][3 * M];
+    const int f = blockIdx.y, tile = blockIdx.x;
+    const float *G = gram + (long)f * n * pitch;
+    const float *X = masks + (long)f * M * n;
+    double accA[M], accC[M], accB[M];
+#pragma unroll
+    for (int m = 0; m < M; ++m) accA[m] = accC[m] = accB[m] = 0.0;
+    const int panel = tile % tl.panels, chunk = tile / tl.panels;
+    const int q = panel * tl.pw + (int)threadIdx.x;
+    if (chunk < tl.chunks && (int)threadIdx.x < tl.pw && q < tl.nq) {
+        float tau_e[4];
+        double lo_e[4], xd[M][4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {                       // columns >= n (the tail of the last quad): a = 0, x = 0
+            const bool ok = 4 * q + e < n;
+            tau_e[e] = ok ? tau : INFINITY;
+            lo_e[e] = ok ? (double)eps : 0.0;
+#pragma unroll
+            for (int m = 0; m < M; ++m) xd[m][e] = ok ? (double)X[(long)m * n + 4 * q + e] : 0.0;
+        }
+        const int r0 = chunk * tl.rows_per_tile, r1 = min(n, r0 + tl.rows_per_tile);
+        const float *gp = G + (long)r0 * pitch + 4 * q;
+        int i = r0;
+        for (; i + 4 <= r1; i += 4, gp += 4 * pitch) {     // four 16-byte loads in flight per thread
+            f32x4 g[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) g[k] = *reinterpret_cast<const f32x4 *>(gp + k * pitch);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) ncut_row<M>(g[k], tau_e, lo_e, xd, X + i + k, n, accA, accC, accB);
+        }
+        for (; i < r1; ++i, gp += pitch)
+            ncut_row<M>(*reinterpret_cast<const f32x4 *>(gp), tau_e, lo_e, xd, X + i, n, accA, accC, accB);
+    }
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+#pragma unroll
+    for (int m = 0; m < M; ++m) {
+        const double a = wave_sum_d(accA[m]), c = wave_sum_d(accC[m]), b = wave_sum_d(accB[m]);
+        if (lane == 0) { red[wv][m] = a; red[wv][M + m] = c; red[wv][2 * M + m] = b; }
+    }
+    __syncthreads();
+    if (threadIdx.x < 3 * M) {
+        const int v = threadIdx.x;
+        partial[((long)f * gridDim.x + tile) * (3 * M) + v] = (red[0][v] + red[1][v]) + (red[2][v] + red[3][v]);
+    }
+}
+
+// out[f][m] = {ncut, cut, assocA, assocB} from the `blocks` partials of frame f, added in a fixed order; one workgroup per frame
+__global__ void __launch_bounds__(256) ncut_finish_kernel(const double *__restrict__ partial, int blocks, int M,
+                                                          double *__restrict__ out) {
+    __shared__ double red[4][3 * NCUT_MAXM];
+    const double *p = partial + (long)blockIdx.x * blocks * (3 * M);
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    for (int v = 0; v < 3 * M; ++v) {
+        double s = 0.0;
+        for (int b = threadIdx.x; b < blocks; b += 256) s += p[(long)b * (3 * M) + v];
+        s = wave_sum_d(s);
+        if (lane == 0) red[wv][v] = s;
+    }
+    __syncthreads();
+    if (threadIdx.x < M) {
+        const int m = threadIdx.x;
+        const double A = (red[0][m] + red[1][m]) + (red[2][m] + red[3][m]);
+        const double C = (red[0][M + m] + red[1][M + m]) + (red[2][M + m] + red[3][M + m]);
+        const double B = (red[0][2 * M + m] + red[1][2 * M + m]) + (red[2][2 * M + m] + red[3][2 * M + m]);
+        double *o = out + ((long)blockIdx.x * M + m) * 4;
+        o[0] = C / A + C / B;                              // IEEE: an all-zero mask gives 0/0 = NaN, like the reference
+        o[1] = C;
+        o[2] = A;
+        o[3] = B;
+    }
+}
+
+// workgroups per frame: 4 per compute unit (a multiple of 256 on the 256-CU part), whatever n is
+int ncut_blocks() {
+    static int blocks = 0;
+    if (!blocks) {
+        int dev = 0, cus = 0;
+        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
+            cus <= 0) {
+            (void)hipGetLastError();
+            cus = 256;
+        }
+        blocks = 4 * cus;
+    }
+    return blocks;
+}
+
+// at most `blocks` tiles: column panels of equal width (<= 256 quads), then as many row chunks as the grid has room for
+ncut_tiling ncut_tiles(int n, int blocks) {
+    ncut_tiling t;
+    t.nq = (n + 3) / 4;
+    t.panels = (t.nq + 255) / 256;
+    t.pw = (t.nq + t.panels - 1) / t.panels;
+    const int want = blocks / t.panels > 0 ? blocks / t.panels : 1;
+    t.rows_per_tile = (n + want - 1) / want;
+    t.chunks = (n + t.rows_per_tile - 1) / t.rows_per_tile;
+    return t;
+}
+
 __global__ void __launch_bounds__(256) clamp01_kernel(float *__restrict__ x, int n) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) x[i] = fminf(fmaxf(x[i], 0.f), 1.f);
@@ -284,6 +424,39 @@ extern "C" int rcf_ncut_value_grad_f32(const float *affinity, long pitch, int n,
     hipLaunchKernelGGL(matvec_kernel, dim3(n), dim3(256), 0, st, affinity, pitch, n, x, u, compute_rowsum ? rowsum : nullptr);
     hipLaunchKernelGGL(ncut_value_grad_kernel, dim3(1), dim3(256), 0, st, x, (const double *)u, (const double *)rowsum, n,
                        grad, value_out);
+    RCF_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" size_t rcf_ncut_values_workspace_bytes(int frames, int n, int M) {
+    if (frames <= 0 || n <= 0 || M < 1 || M > NCUT_MAXM) return 0;
+    return (size_t)frames * ncut_blocks() * 3 * M * sizeof(double);
+}
+
+/* the soft-NCut terms of M masks per frame, in one pass over the RAW Gram matrices gram[frames][n][pitch] (read only; the
+ * threshold a = g > tau ? 1 : eps is applied in registers): out[frames][M][4] = {ncut, cut, assocA, assocB} in fp64.
+ * masks[frames][M][n]; 1 <= M <= 8; pitch % 4 == 0, gram 16-byte aligned.  Deterministic (no atomics). */
+extern "C" int rcf_ncut_values_f32(const float *gram, long pitch, int n, int frames, float tau, float eps, const float *masks,
+                                   int M, double *out, void *workspace, size_t workspace_bytes, void *stream) {
+    if (!gram || !masks || !out || !workspace || frames <= 0 || frames > 65535 || n <= 0 || M < 1 || M > NCUT_MAXM || pitch < n ||
+        pitch % 4 || !rcf_aligned16(gram))
+        return RCF_EINVAL;
+    if (workspace_bytes < rcf_ncut_values_workspace_bytes(frames, n, M)) return RCF_EWORKSPACE;
+    const int blocks = ncut_blocks();
+    const ncut_tiling tl = ncut_tiles(n, blocks);
+    if ((long)tl.panels * tl.chunks > blocks) return RCF_EINVAL;
+    hipStream_t st = rcf_stream(stream);
+    double *partial = (double *)workspace;
+#define NCUT_LAUNCH(MM)                                                                                                    \
+    case MM:                                                                                                               \
+        hipLaunchKernelGGL(ncut_values_kernel<MM>, dim3(blocks, frames), dim3(256), 0, st, gram, pitch, n, tau, eps, masks, tl, \
+                           partial);                                                                                       \
+        break;
+    switch (M) {
+        NCUT_LAUNCH(1) NCUT_LAUNCH(2) NCUT_LAUNCH(3) NCUT_LAUNCH(4) NCUT_LAUNCH(5) NCUT_LAUNCH(6) NCUT_LAUNCH(7) NCUT_LAUNCH(8)
+    }
+#undef NCUT_LAUNCH
+    hipLaunchKernelGGL(ncut_finish_kernel, dim3(frames), dim3(256), 0, st, (const double *)partial, blocks, M, out);
     RCF_LAUNCH_CHECK();
     return 0;
 }

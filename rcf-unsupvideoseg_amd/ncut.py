@@ -9,6 +9,9 @@ gradient:  with s = A 1, a = s.x, S = sum s, cut = a - x.u,
     NCut = cut/a + cut/(S-a),     dNCut/dx = (s - 2u)(1/a + 1/(S-a)) - cut s/a^2 + cut s/(S-a)^2
 (A is symmetric).  Reductions in fp64; the Adam update is the fused kernel of the trainer (coupled weight decay, like
 torch.optim.Adam).
+
+MAA (rcf_amd.maa) scores several masks per frame and never refines them: `soft_ncut_values` / `NCutEvalHead.forward_multi`
+leave the Gram matrix raw and get the NCut terms of all masks from one pass over it (rcf_ncut_values_f32).
 """
 import torch
 import torch.nn as nn
@@ -52,6 +55,40 @@ def soft_ncut_value(feats, mask, tau, eps):
     """semantic_constraints.py:21-41 / maa.py:19-36: feats [1,T,C], mask [h,w] -> 0-dim NCut value"""
     x = mask.reshape(-1).contiguous().float()
     return _NCut(feats, tau, eps).value_grad(x).clone()[0]
+
+
+MAX_MASKS = 8           # masks per rcf_ncut_values_f32 call (include/rcf_hip.h)
+
+
+@torch.no_grad()
+def soft_ncut_values(feats, masks, tau, eps, return_terms=False):
+    """The soft NCut (maa.py:19-36) of M masks on each of F frames: feats [F,T,C] (row 0 of a frame = [CLS], dropped), masks
+    [F,M,h,w] with h*w == T-1 -> float64 [F,M]; with `return_terms` [F,M,4] = (ncut, cut, assocA, assocB).  One row
+    normalisation, one Gram product per frame and ONE pass over the raw Gram matrices for all masks (rcf_ncut_values_f32):
+    the matrices are neither thresholded in memory nor read once per mask.  More than 8 masks go in groups of 8."""
+    F_, T, C = feats.shape
+    n = T - 1
+    assert masks.shape[0] == F_ and masks[0, 0].numel() == n, f"masks {tuple(masks.shape)} do not fit features {tuple(feats.shape)}"
+    M = masks.shape[1]
+    f = feats[:, 1:, :].contiguous().float()
+    fn = ops.l2_normalize_rows(f.view(F_ * n, C)).view(F_, n, C)        # F.normalize(p=2, dim=1), every frame at once
+    npad = (n + 3) // 4 * 4
+    G = torch.empty((F_, n, npad), dtype=torch.float32, device=f.device)
+    for b in range(F_):
+        ops.gemm_nt(fn[b], fn[b], out=G[b, :, :n])
+    x = masks.reshape(F_, M, n).float()
+    out = torch.empty((F_, M, 4), dtype=torch.float64, device=f.device)
+    lib = _lib.load()
+    for m0 in range(0, M, MAX_MASKS):
+        xm = x[:, m0:m0 + MAX_MASKS].contiguous()
+        mm = xm.shape[1]
+        o = torch.empty((F_, mm, 4), dtype=torch.float64, device=f.device)
+        nbytes = lib.rcf_ncut_values_workspace_bytes(F_, n, mm)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=f.device)
+        _lib.call("rcf_ncut_values_f32", _p(G), npad, n, F_, float(tau), float(eps), _p(xm), mm, _p(o), _p(ws), nbytes,
+                  _stream())
+        out[:, m0:m0 + mm] = o
+    return out if return_terms else out[..., 0].contiguous()
 
 
 @torch.no_grad()
@@ -135,3 +172,13 @@ class NCutEvalHead(_NCutBase):
         imgs, small = self._inputs(imgs, masks, standardize)
         feats = self.get_feats(imgs)
         return soft_ncut_value(feats, small[0], self.tau, self.eps)[None].cpu().numpy()
+
+    @torch.no_grad()
+    def forward_multi(self, imgs, masks, standardize=False):
+        """imgs [F,H,W,3] (standardize=True) or [F,3,H,W], masks [F,M,H,W] -> numpy float64 [F,M]: the value `forward` gives
+        for frame f and mask m, from one ViT forward and one Gram product per frame (soft_ncut_values)"""
+        F_, M = masks.shape[:2]
+        imgs, small = self._inputs(imgs, masks.reshape((F_ * M,) + tuple(masks.shape[2:])), standardize)
+        feats = self.get_feats(imgs)
+        small = small.view(F_, M, self.h_featuremap, self.w_featuremap)
+        return soft_ncut_values(feats, small, self.tau, self.eps).cpu().numpy()

@@ -5,6 +5,7 @@ box produce identical bytes.  seed = 1000 * config_id + sample_index for data; w
 have their own seed.  No dataset or checkpoint exists in either environment.
 """
 import numpy as np
+import torch
 
 IMAGENET_MEAN = np.array([0.485, 0.456, 0.406], dtype=np.float32)   # dataset/transforms.py:893
 IMAGENET_STD = np.array([0.229, 0.224, 0.225], dtype=np.float32)
@@ -274,6 +275,132 @@ def davis_tree(root, seed=2016, step=0):
     with open(os.path.join(root, "ImageSets", "480p", "val.txt"), "w") as f:
         f.writelines(lines)
     return root, res
+
+
+# ---- MAA (motion-appearance alignment, rcf_amd.maa): inputs on which the soft NCut tells masks apart -----------------------
+# The seeded ViT weights give nearly identical tokens (affinity all ones, NCut == 1 for every mask), so these fixtures
+# bring their own features: clustered keys laid out as spatial regions.
+
+
+def maa_regions(hf, wf):
+    """int [hf,wf] region labels: background 0, a rectangle 1, an ellipse 2, a bottom band 3"""
+    yy, xx = np.mgrid[:hf, :wf]
+    lab = np.zeros((hf, wf), dtype=np.int64)
+    lab[yy >= hf - max(1, hf // 6)] = 3
+    lab[(yy >= hf // 8) & (yy < hf // 8 + max(1, hf // 3)) & (xx >= wf // 10) & (xx < wf // 10 + max(1, wf // 4))] = 1
+    cy, cx, ry, rx = 0.5 * hf, 0.68 * wf, max(1.0, 0.22 * hf), max(1.0, 0.18 * wf)
+    lab[((yy - cy) / ry) ** 2 + ((xx - cx) / rx) ** 2 < 1.0] = 2
+    return lab
+
+
+def maa_features(seed, hf, wf, noise, dim=384):
+    """f32 [1, 1 + hf*wf, dim]: a [CLS] row, then one key per cell = the centre of the cell's region (maa_regions) +
+    `noise` * N(0, 1).  Centres are N(0, 1), so keys of one region have cosine ~ 1 / (1 + noise^2) and keys of two
+    regions ~ 0: noise 1.2 puts the two modes at 0.41 / 0 around tau = 0.2, noise 2.0 puts the upper mode ON tau."""
+    g = _rng(seed)
+    lab = maa_regions(hf, wf).reshape(-1)
+    centers = g.standard_normal((4, dim))
+    fe = centers[lab] + noise * g.standard_normal((hf * wf, dim))
+    return np.concatenate([g.standard_normal((1, dim)), fe])[None].astype(np.float32)
+
+
+def maa_masks(seed, hf, wf, M):
+    """f32 [M,hf,wf], values in (0, 1): mask 0 aligned with regions 1 + 2 of maa_regions (~0.9 inside, ~0.1 outside), 1 a
+    shifted copy of it, 2 uniform random, 3 constant; masks 4.. repeat the four kinds on other regions / shifts / draws /
+    levels.  Levels and shifts come from the seed."""
+    g = _rng(seed)
+    lab = maa_regions(hf, wf)
+    out = []
+    for m in range(M):
+        kind, rep = m % 4, m // 4
+        hi, lo, level = 0.85 + 0.1 * g.random(), 0.05 + 0.1 * g.random(), g.uniform(0.3, 0.7)
+        dy, dx = max(1, hf // 4) + int(g.integers(0, 3)), max(1, wf // 4) + int(g.integers(0, 3))
+        inside = ((lab == 1) | (lab == 2)) if rep == 0 else (lab == 1 + rep % 3)
+        if kind == 0:
+            x = np.where(inside, hi, lo)
+        elif kind == 1:
+            x = np.roll(np.where((lab == 1) | (lab == 2), hi, lo), (dy, dx), axis=(0, 1))
+        elif kind == 2:
+            x = g.uniform(0.05, 0.95, size=(hf, wf))
+        else:
+            x = np.full((hf, wf), level)
+        out.append(x)
+    return np.stack(out).astype(np.float32)
+
+
+class PatchFeatures(torch.nn.Module):
+    """A stand-in for the DINO ViT with the one method the NCut heads call, get_last_qkv(imgs [B,3,H,W], which) ->
+    [B, 1 + (H/8)(W/8), dim]: the mean colour of every 8x8 patch goes through a seeded random projection and a cosine
+    (random Fourier features of a Gaussian kernel of width 1/scale in standardised colour units), plus a [CLS] row.
+    Patches of one flat colour map to one point, patches of colours further apart than ~1/scale to nearly orthogonal
+    ones: the Gram values of an image of flat regions are bimodal (~1 / ~0) around tau.  Plain torch, CPU or GPU: it is a
+    test input, not a product path."""
+
+    def __init__(self, seed=31, dim=384, patch_size=8, scale=3.0):
+        super().__init__()
+        g = _rng(seed)
+        self.patch_size, self.embed_dim = patch_size, dim
+        self.register_buffer("proj", torch.from_numpy((scale * g.standard_normal((dim, 3))).astype(np.float32)))
+        self.register_buffer("phase", torch.from_numpy(g.uniform(0, 2 * np.pi, size=dim).astype(np.float32)))
+        self.register_buffer("cls", torch.from_numpy(g.standard_normal(dim).astype(np.float32)))
+
+    @torch.no_grad()
+    def get_last_qkv(self, imgs, which="k"):
+        assert which in ("q", "k", "v"), which
+        c = torch.nn.functional.avg_pool2d(imgs.float(), self.patch_size)            # [B,3,hf,wf]
+        c = c.flatten(2).transpose(1, 2)                                             # [B,n,3]
+        f = torch.cos(c @ self.proj.T + self.phase)
+        return torch.cat([self.cls.expand(c.shape[0], 1, -1), f], dim=1)
+
+
+MAA_TREE = (("blackswan", 3, None), ("camel", 2, (240, 427)), ("dog", 3, None))   # (DAVIS val sequence, frames, export size)
+MAA_TREE_CHANNELS, MAA_TREE_OBJECT = 3, 1
+
+
+def _maa_frame(g, si, t):
+    """u8 [480,854,3] frame of flat coloured rectangles with N(0, 2) noise, and the bool [480,854] object rectangle"""
+    H, W = 480, 854
+    bg = np.array([(60, 140, 70), (150, 130, 90), (70, 90, 160)][si], dtype=np.float32)
+    obj = np.array([(220, 60, 50), (40, 60, 200), (230, 210, 60)][si], dtype=np.float32)
+    other = np.array([(30, 30, 40), (240, 240, 235), (120, 30, 130)][si], dtype=np.float32)
+    img = np.empty((H, W, 3), dtype=np.float32)
+    img[:] = bg
+    img[392:, :] = other                                            # a band that is neither object nor background
+    y0, x0 = 96 + 16 * si, 150 + 120 * si + 40 * t                  # the object moves 40 px per frame
+    m = np.zeros((H, W), dtype=bool)
+    m[y0:y0 + 184, x0:x0 + 240] = True
+    img[m] = obj
+    img += g.normal(0, 2.0, size=img.shape).astype(np.float32)
+    return np.clip(img + 0.5, 0, 255).astype(np.uint8), m
+
+
+def maa_tree(root, seed=77, step=0):
+    """A synthetic DAVIS tree for rcf_amd.maa under `root`: root/data/data_davis/JPEGImages/480p/{seq}/{frame:05}.jpg (real
+    480x854 JPEGs of flat coloured regions with mild noise) and root/saved_eval_export/{channel}/pred_seg_{seq}_{frame}_
+    {step:07}.png for 3 channels (RGB PNG; one sequence exported at 240x427, so the loader's resize runs).  Channel
+    MAA_TREE_OBJECT is aligned with the coloured object in every frame (230 inside / 25 outside); channel 0 is the same
+    rectangle shifted by half its size, channel 2 the complement of a copy shifted the other way.
+    Returns (pretrain_dir, data_dir) = (root, root/data)."""
+    import os
+    from PIL import Image
+    g = _rng(seed)
+    images = os.path.join(root, "data", "data_davis", "JPEGImages", "480p")
+    for ch in range(MAA_TREE_CHANNELS):
+        os.makedirs(os.path.join(root, "saved_eval_export", str(ch)), exist_ok=True)
+    for si, (seq, T, size) in enumerate(MAA_TREE):
+        os.makedirs(os.path.join(images, seq), exist_ok=True)
+        for t in range(T):
+            fid = f"{t:05d}"
+            img, m = _maa_frame(g, si, t)
+            Image.fromarray(img).save(os.path.join(images, seq, fid + ".jpg"), quality=95)
+            chans = (np.roll(m, (92, 120), axis=(0, 1)), m, ~np.roll(m, (-70, -160), axis=(0, 1)))
+            for ch, cm in enumerate(chans):
+                p = np.where(cm, 230, 25).astype(np.uint8)
+                im = Image.fromarray(np.stack([p, p, p], -1))
+                if size is not None:
+                    im = im.resize((size[1], size[0]), resample=Image.NEAREST)
+                im.save(os.path.join(root, "saved_eval_export", str(ch), f"pred_seg_{seq}_{fid}_{step:07}.png"))
+    return root, os.path.join(root, "data")
 
 
 def fill_state_dict(shapes, seed=7, bn3_gamma=0.5, seg_scale=10.0):
