@@ -765,6 +765,35 @@ size_t rcf_ncut_values_workspace_bytes(int frames, int n, int M);
 int rcf_ncut_values_f32(const float *gram, long pitch, int n, int frames, float tau, float eps, const float *masks, int M,
                         double *out, void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- semantic-constraint refinement for a batch of frames (tools/SemanticConstraintsAndMAA/semantic_constraints.py:21-75,
+ * 299-336; csrc/semantic.hip) ---------------------------------------------------------------------------------------------
+ * rcf_affinity_pack_f32: ONE read-only pass over the raw Gram matrices gram[frames][n][pitch] (pitch >= n, no alignment asked):
+ * bit j of row i is set when gram_ij > tau (strict; a NaN gives 0), no symmetry assumed.  bits[frames][n][W] 32-bit words with
+ * W = rcf_affinity_pack_words(n) = 2 ceil(n / 64) (bit j of a row = bit j % 32 of word j / 32; every bit from n on is 0; bits
+ * 8-byte aligned); deg[frames][n] = the popcount of the row.  The bit matrix of a 6 420-token frame takes 5.2 MB. */
+int rcf_affinity_pack_words(int n);
+int rcf_affinity_pack_f32(const float *gram, long pitch, int n, int frames, float tau, uint32_t *bits, int32_t *deg, void *stream);
+/* rcf_ncut_refine_packed_f32: `steps` Adam steps on the soft NCut of x[frames][n] (in place) against the affinity
+ * a_ij = (bit ij ? 1 : eps) given as packed bits + row popcounts, for every frame of the batch.  With e = (double)eps:
+ * u_i = e sum_j x_j + (1 - e) sum_{j in row i} x_j,  s_i = e n + (1 - e) deg_i,  value and gradient as rcf_ncut_value_grad_f32
+ * (closed form, fp64), then the arithmetic of rcf_adam_step_f32 (betas 0.9 / 0.999, eps 1e-8, coupled weight decay, bias
+ * correction with the step number) and a clamp to [0, 1].  Two launches per step for the whole batch (row sums: grid.y = frame;
+ * value + gradient + Adam + clamp: one workgroup per frame); steps are separated by kernel boundaries only.  Reductions are
+ * fp64 in a fixed order without atomics: a frame's result depends neither on `frames` nor on its position and is the same
+ * bits on every run.  values (may be NULL): [frames][steps] fp64, the NCut BEFORE each step.  steps == 0 leaves x untouched.
+ * n <= RCF_NCUT_PACKED_MAX_N (x of a frame sits in LDS); a larger n is RCF_EINVAL before any launch.  workspace: 8-byte aligned. */
+#define RCF_NCUT_PACKED_MAX_N 16384
+size_t rcf_ncut_refine_packed_workspace_bytes(int frames, int n);
+int rcf_ncut_refine_packed_f32(const uint32_t *bits, const int32_t *deg, int n, int frames, float eps, float *x, int steps,
+                               float lr, float weight_decay, double *values, void *workspace, size_t workspace_bytes,
+                               void *stream);
+/* The CRF / NCut-CRF merge (semantic_constraints.py:314-336) of a, b [frames][npix] fp32: counts[f] = |(a > 0.5) xor (b > 0.5)|
+ * (the union minus the intersection; int64, written by the call), out[f] = trunc(fl32(fl32(a b) 255)) as u8 -- or
+ * trunc(fl32(a 255)) for a frame with counts[f] > umi_th (strict).  umi_th < 0: no threshold.  Two empty masks give the product
+ * (the reference's NaN > th is false).  The counts are added with integer atomics: order-independent. */
+int rcf_mask_merge_u8(const float *a, const float *b, int frames, long npix, long long umi_th, uint8_t *out, long long *counts,
+                      void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -115,6 +115,11 @@ PROTOS = {
     "rcf_clamp01_f32": (c_int, [P, c_int, P]),
     "rcf_ncut_values_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "rcf_ncut_values_f32": (c_int, [P, c_long, c_int, c_int, c_float, c_float, P, c_int, P, P, c_size_t, P]),
+    "rcf_affinity_pack_words": (c_int, [c_int]),
+    "rcf_affinity_pack_f32": (c_int, [P, c_long, c_int, c_int, c_float, P, P, P]),
+    "rcf_ncut_refine_packed_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "rcf_ncut_refine_packed_f32": (c_int, [P, P, c_int, c_int, c_float, P, c_int, c_float, c_float, P, P, c_size_t, P]),
+    "rcf_mask_merge_u8": (c_int, [P, P, c_int, c_long, ctypes.c_longlong, P, P, P]),
     "rcf_split_rect_f32": (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P]),
     "rcf_absmax_f32": (c_int, [P, c_long, c_int, c_int, P, P]),
     "rcf_conv_weight_pairs_f32": (c_int, [P, c_int, c_int, c_int, c_int, P, P, c_uint, P]),

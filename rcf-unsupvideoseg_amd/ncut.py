@@ -12,6 +12,10 @@ torch.optim.Adam).
 
 MAA (rcf_amd.maa) scores several masks per frame and never refines them: `soft_ncut_values` / `NCutEvalHead.forward_multi`
 leave the Gram matrix raw and get the NCut terms of all masks from one pass over it (rcf_ncut_values_f32).
+
+The semantic-constraint driver (rcf_amd.semantic) refines every exported mask: `ncut_refine_batch` / `NCutHead.forward_batch`
+pack the thresholded affinity of each frame into a bit matrix (rcf_affinity_pack_f32: one read of the Gram, 1/32 of its bytes
+written) and run all Adam steps of all frames of a batch on it (rcf_ncut_refine_packed_f32: two launches per step).
 """
 import torch
 import torch.nn as nn
@@ -108,6 +112,65 @@ def ncut_refine(feats, masks, tau=0.2, eps=1e-5, steps=10, learning_rate=1e-1, w
     return x.view(shape)
 
 
+MAX_PACKED_N = 16384    # RCF_NCUT_PACKED_MAX_N (include/rcf_hip.h)
+
+
+def pack_words(n):
+    """32-bit words per row of the packed affinity (rcf_affinity_pack_words)"""
+    return 2 * ((n + 63) // 64)
+
+
+def affinity_pack(gram, n, tau, bits=None, deg=None):
+    """gram [F, n, pitch] (or [n, pitch]) raw Gram matrices -> (bits int32 [F, n, pack_words(n)], deg int32 [F, n]): bit j of
+    row i = gram_ij > tau, deg = the popcount of the row (rcf_affinity_pack_f32; the Gram matrices are only read)"""
+    g = gram if gram.dim() == 3 else gram[None]
+    F_, rows, pitch = g.shape
+    assert rows == n and g.stride(2) == 1 and g.stride(1) == pitch and (F_ == 1 or g.stride(0) == n * pitch) and g.dtype == torch.float32
+    if bits is None:
+        bits = torch.empty((F_, n, pack_words(n)), dtype=torch.int32, device=g.device)
+        deg = torch.empty((F_, n), dtype=torch.int32, device=g.device)
+    _lib.call("rcf_affinity_pack_f32", _p(g), pitch, n, F_, float(tau), _p(bits), _p(deg), _stream())
+    return bits, deg
+
+
+def refine_packed(bits, deg, x, eps, steps, learning_rate, weight_decay, return_values=False):
+    """`steps` Adam steps on x [F, n] (in place) against the packed affinities of its frames (rcf_ncut_refine_packed_f32);
+    with `return_values` also float64 [F, steps]: the NCut before each step"""
+    F_, n = x.shape
+    assert x.is_contiguous() and x.dtype == torch.float32 and tuple(bits.shape) == (F_, n, pack_words(n)) and tuple(deg.shape) == (F_, n)
+    values = torch.empty((F_, steps), dtype=torch.float64, device=x.device) if return_values else None
+    nbytes = _lib.load().rcf_ncut_refine_packed_workspace_bytes(F_, n)
+    ws = torch.empty(max(nbytes, 8), dtype=torch.uint8, device=x.device)
+    _lib.call("rcf_ncut_refine_packed_f32", _p(bits), _p(deg), n, F_, float(eps), _p(x), int(steps), float(learning_rate),
+              float(weight_decay), _p(values) if steps > 0 else None, _p(ws), nbytes, _stream())
+    return (x, values) if return_values else x
+
+
+@torch.no_grad()
+def ncut_refine_batch(feats, masks, tau=0.2, eps=1e-5, steps=10, learning_rate=1e-1, weight_decay=1e-6, return_values=False):
+    """`ncut_refine` for F frames at once: feats [F,T,C] (row 0 of a frame = [CLS], dropped), masks [F,h,w] with h*w == T-1 ->
+    refined masks [F,h,w] (with `return_values` also float64 [F, steps], the NCut before each step).  One row normalisation
+    for all frames; per frame a Gram product into ONE buffer that the next frame reuses on the stream, packed to bits at once;
+    then every Adam step of every frame in 2 * steps launches."""
+    F_, T, C = feats.shape
+    n = T - 1
+    assert masks.shape[0] == F_ and masks[0].numel() == n, f"masks {tuple(masks.shape)} do not fit features {tuple(feats.shape)}"
+    f = feats[:, 1:, :].contiguous().float()
+    fn = ops.l2_normalize_rows(f.view(F_ * n, C)).view(F_, n, C)        # F.normalize(p=2, dim=1), every frame at once
+    npad = (n + 3) // 4 * 4
+    G = torch.empty((n, npad), dtype=torch.float32, device=f.device)
+    bits = torch.empty((F_, n, pack_words(n)), dtype=torch.int32, device=f.device)
+    deg = torch.empty((F_, n), dtype=torch.int32, device=f.device)
+    for b in range(F_):
+        ops.gemm_nt(fn[b], fn[b], out=G[:, :n])
+        affinity_pack(G, n, tau, bits[b:b + 1], deg[b:b + 1])
+    x = masks.reshape(F_, n).float().clone()
+    out = refine_packed(bits, deg, x, eps, steps, learning_rate, weight_decay, return_values)
+    if return_values:
+        return out[0].view(masks.shape), out[1]
+    return out.view(masks.shape)
+
+
 class _NCutBase(nn.Module):
     def __init__(self, args, resize_imgs_size=(480, 856), resize_masks_size=(480, 854), arch="vit_small", patch_size=8,
                  which_features="k", tau=0.2, eps=1e-5, mean=(0.485, 0.456, 0.406), std=(0.229, 0.224, 0.225), model=None):
@@ -161,6 +224,19 @@ class NCutHead(_NCutBase):
         # refined image by image here
         out = torch.stack([ncut_refine(feats[b:b + 1], small[b], self.tau, self.eps, self.steps, self.learning_rate,
                                        self.weight_decay) for b in range(feats.shape[0])])
+        return ops.resize_nchw(out[:, None].contiguous(), self.resize_masks_size, False)[:, 0].float()
+
+    @torch.no_grad()
+    def refine_batch(self, imgs, masks, standardize=False):
+        """the feature-map sized refined masks [B, hf, wf] of `forward_batch` (before the final resize)"""
+        imgs, small = self._inputs(imgs, masks, standardize)
+        feats = self.get_feats(imgs)
+        return ncut_refine_batch(feats, small, self.tau, self.eps, self.steps, self.learning_rate, self.weight_decay)
+
+    @torch.no_grad()
+    def forward_batch(self, imgs, masks, standardize=False):
+        """`forward` with the frames of the batch refined together: one ViT forward, then ncut_refine_batch"""
+        out = self.refine_batch(imgs, masks, standardize)
         return ops.resize_nchw(out[:, None].contiguous(), self.resize_masks_size, False)[:, 0].float()
 
 

@@ -5,6 +5,8 @@
 * `double_crf_merge`: the CRF / NCut-CRF merge of tools/SemanticConstraintsAndMAA/semantic_constraints.py:299-324
   (`crf_head_single`, crf_scale 0.7, on the input mask; `crf_head`, crf_scale 0.5, on the refined mask; product, or
   the single-CRF mask when the two disagree by more than `umi_th`).
+* `double_crf_merge_u8`: the same for a batch of frames, ending in the u8 image the driver saves (rcf_mask_merge_u8: the
+  disagreement counts and the bytes on the device, no host round trip); the route of rcf_amd.semantic.
 
 `refine` reproduces pydensecrf's arithmetic: DenseCRF2D.addPairwiseBilateral's default SYMMETRIC kernel normalisation
 (N^1/2 K N^1/2, Kraehenbuehl & Koltun's densecrf), selected in the HIP kernel by rcf_crf_soft_ex(normalization=1); the
@@ -72,3 +74,19 @@ def double_crf_merge(crf_head_single, crf_head, images, masks, refined_masks, um
         if umi(a[i].cpu().numpy() > 0.5, b[i].cpu().numpy() > 0.5) > umi_th:
             out[i] = a[i]                                # likely captures different things: keep the single CRF
     return out
+
+
+@torch.no_grad()
+def double_crf_merge_u8(crf_head_single, crf_head, images, masks, refined_masks, umi_th=None, return_counts=False):
+    """`double_crf_merge` as the u8 image the driver saves, (merged * 255).astype(uint8) of semantic_constraints.py:335-336: u8
+    [n,H,W] on the device.  Both CRFs run batched and rcf_mask_merge_u8 counts the union minus the intersection of every frame
+    and writes the bytes: nothing goes to the host.  `return_counts`: also int64 [n], the counts."""
+    from . import _lib
+    from .ops import _p, _stream
+    a = crf_head_single(images, masks, unstandardize=False).contiguous()
+    b = crf_head(images, refined_masks, unstandardize=False).contiguous()
+    n, H, W = a.shape
+    out = torch.empty((n, H, W), dtype=torch.uint8, device=a.device)
+    counts = torch.empty(n, dtype=torch.int64, device=a.device)
+    _lib.call("rcf_mask_merge_u8", _p(a), _p(b), n, H * W, -1 if umi_th is None else int(umi_th), _p(out), _p(counts), _stream())
+    return (out, counts) if return_counts else out
