@@ -597,6 +597,14 @@ int rcf_crf_hard(const uint8_t *rgb, const int16_t *label, int W, int H, int bat
 int rcf_crf_prepare(const float *img_nchw, const float *mask, const float *mean3, const float *std3,
                     int unstandardize, float crf_scale, uint8_t *rgb_out, float *unary_out, uint32_t *scratch,
                     int batch, int H, int W, void *stream);
+/* Unary energies of the pydenseCRF post-processor (tools/pydenseCRF/crf.py:60-68) from u8 masks [frames][npix], by table:
+ * unary[f][p][:] = table[max_f][mask[f][p]][:], max_f the largest byte of frame f.  table: [256][256][2] fp32 on the device, indexed
+ * (frame maximum, pixel value) -- the caller tabulates the host's float64 steps (divide by the maximum + 1e-8, clip, -log(1 - U),
+ * -log(U); any monotone pre-scaling of the bytes composed in), so the device copies the host's bits and evaluates no function.
+ * unary: [frames][npix][2] fp32, the layout rcf_crf_soft takes.  scratch: frames uint32 (per-frame maximum; zeroed by the call).
+ * npix needs no alignment (the mask is read in aligned 16-byte pieces wherever a frame starts); table and unary 8-byte aligned. */
+int rcf_crf_unary_lut_u8(const uint8_t *mask, int frames, long npix, const float *table, float *unary, uint32_t *scratch,
+                         void *stream);
 
 /* ---- flow-aggregation head (relaxed common fate) + loss tail ------------------------------------
  * models/flow_aggregation_head_with_residual.py:235-310 (aggregate), :164-233 (per-segment affine

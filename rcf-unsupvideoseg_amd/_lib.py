@@ -186,6 +186,7 @@ PROTOS = {
     "rcf_crf_hard": (c_int, [P, P, c_int, c_int, c_int, c_float, c_float, c_float, c_float, c_float, c_float, c_int,
                              P, P, P, P, c_size_t, P]),
     "rcf_crf_prepare": (c_int, [P, P, P, P, c_int, c_float, P, P, P, c_int, c_int, c_int, P]),
+    "rcf_crf_unary_lut_u8": (c_int, [P, c_int, c_long, P, P, P, P]),
     "rcf_flowhead_workspace_bytes": (c_size_t, [_FH]),
     "rcf_flowhead_prepare_f32": (c_int, [_FH, P, P, P, P, c_size_t, P]),
     "rcf_flowhead_fwd_f32": (c_int, [_FH] + [P] * 15 + [P, c_size_t, P]),
