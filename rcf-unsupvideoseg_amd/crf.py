@@ -10,6 +10,13 @@ from . import _lib
 from .ops import _p, _stream, workspace
 
 
+# The per-call switches of rcf_crf_soft_ex as crf_soft_batched's `build=` takes them: the RCF_CRF_* macros of include/rcf_hip.h,
+# shifted down past the normalisation byte (`build` is `normalization >> 8`).  Every combination gives bit-identical results.
+BUILD_ARRAY, BUILD_SMALL_TABLE, BUILD_SORT = 1, 2, 3     # the lattice build: one two-bit field (0 = the default)
+BLUR_SEQUENTIAL = 4
+SPLAT_GATHER, SPLAT_TILES, SLICE_SPLAT_SEPARATE = 0x40, 0x80, 0x100
+
+
 def _check(t, name):
     if not t.is_cuda:
         raise RuntimeError(f"{name} must be a CUDA tensor")          # CHECK_CUDA, torchcrf.cu:18
@@ -22,7 +29,8 @@ def crf_soft_batched(rgb_u8, unary, W, H, scomp_smooth, sxy_smooth, scomp_app, s
     """rgb_u8 [n,H,W,3] uint8 (or float32: the features as they are, rcf_crf_soft_f32), unary [n,H*W,2] f32 -> MAP int16 [n,H,W]
     (+ Q [n,H*W,2], nvert [n,2]).
     symmetric: pydensecrf's DenseCRF2D kernel normalisation (NORMALIZE_SYMMETRIC) instead of tools/torchCRF's.
-    build: 0 default, 1 RCF_CRF_BUILD_ARRAY, 2 RCF_CRF_BUILD_SMALL_TABLE, 3 RCF_CRF_BUILD_SORT (identical results)"""
+    build: 0 default, or the switches above OR-ed together -- one of BUILD_ARRAY / BUILD_SMALL_TABLE / BUILD_SORT, BLUR_SEQUENTIAL,
+    SPLAT_GATHER / SPLAT_TILES, SLICE_SPLAT_SEPARATE (identical results)"""
     _check(rgb_u8, "rgbFeat")
     _check(unary, "unaryEnergy")
     n = rgb_u8.shape[0]
@@ -106,7 +114,7 @@ class CRFHead(nn.Module):
 
     def _pick_build(self, npix):
         if self.sort_build != "auto":
-            return 3 if self.sort_build else 0
+            return BUILD_SORT if self.sort_build else 0
         if self._nv_host is not None:
             # whatever the last completed copy left there (zeros before the first one): a count that is one or two calls old
             # serves a heuristic as well as a fresh one, and no event / query is needed (a recorded event per call cost
@@ -114,7 +122,7 @@ class CRFHead(nn.Module):
             verts = float(self._nv_host[:, 1].float().mean())
             if verts > 0:
                 self._sorting = verts > (self.SORT_BELOW if self._sorting else self.SORT_ABOVE) * 6 * npix
-        return 3 if self._sorting else 0
+        return BUILD_SORT if self._sorting else 0
 
     def _note_counts(self, nv):
         if self._nv_host is None or self._nv_host.shape[0] != nv.shape[0]:
@@ -154,7 +162,7 @@ class CRFHead(nn.Module):
         N, H, W, _ = rgb.shape
         auto = self.sort_build == "auto"
         self.last_build = self._pick_build(H * W)
-        if self.last_build == 3 and N > 16:
+        if self.last_build == BUILD_SORT and N > 16:
             self.last_build = 0              # csrc/crf.hip build_lattice: the sort build takes at most 16 frames per call (4 frame
                                              # bits beside the 60 key bits) -- report the build that runs, not the one asked for
         m = crf_soft_batched(rgb, unary, W, H, self.scomp_smooth, self.sxy_smooth, self.scomp, self.sxy, self.srgb,

@@ -24,12 +24,17 @@
 //  * persistent caller-owned workspace, all frames of a batch in every launch (grid.y = frame).
 //  Algorithmic bytes per iteration: 192*N + 348*L, L = lattice vertices.
 #include "rcf_common.h"
+#include <type_traits>
+#include <utility>
 
 namespace {
 
 constexpr int MLAB = 2;
 constexpr int PD_MAX = 5;
 constexpr double FIX_SCALE = 1099511627776.0;   // 2^40
+// the lattice build is a two-bit field of rcf_crf_soft_ex's `normalization` (RCF_CRF_BUILD_SORT sets both bits)
+constexpr int BUILD_FIELD = RCF_CRF_BUILD_ARRAY | RCF_CRF_BUILD_SMALL_TABLE;
+static_assert(RCF_CRF_BUILD_SORT == BUILD_FIELD, "ARRAY, SMALL_TABLE and SORT are the three values of one field");
 
 struct Lattice {           // device pointers of one potential, for all frames (frame stride in elements)
     int pd;
@@ -37,10 +42,12 @@ struct Lattice {           // device pointers of one potential, for all frames (
     int W;                 // image width (N = W * H): the per-pixel kernels walk 16 x 16 tiles
     long E;                // entries per frame = N*(pd+1)
     float w;               // Potts weight
-    int tune;              // per call (rcf_crf_soft_ex `normalization` bits 10-15): bit 0 RCF_CRF_BLUR_SEQUENTIAL (one launch per blur
-                           // axis instead of one per PAIR of axes), bits 1-3 the vertex kernels' grid (lab: 0 = the default)
-    int build;             // per call (rcf_crf_soft_ex `normalization` bits): 0 packed build when the keys fit, 1 always the
-                           // array-of-keys build, 2 packed build whose first-attempt table is tiny (exercises the overflow path)
+    int opts;              // per call: rcf_crf_soft_ex's `normalization` as the caller passed it.  The public bits are tested where they
+                           // act: RCF_CRF_BLUR_SEQUENTIAL (one launch per blur axis instead of one per PAIR of axes), RCF_CRF_SPLAT_GATHER,
+                           // RCF_CRF_SPLAT_TILES (tile_mode), RCF_CRF_SLICE_SPLAT_SEPARATE (crf_infer); the build bits travel in `build`
+    int build;             // per call, host side: the BUILD_FIELD of `normalization`: 0 packed build when the keys fit, RCF_CRF_BUILD_ARRAY
+                           // always the array-of-keys build (also every rcf_crf_soft_f32 call), RCF_CRF_BUILD_SMALL_TABLE packed build whose
+                           // first-attempt table is tiny (exercises the overflow path), RCF_CRF_BUILD_SORT the sort build
     uint4 *keys;           // [F][E]   5 x int16 packed, zero padded
     float *weight;         // [F][E]
     int *entries;          // [F][2E]  bucket -> representative slot (-1 empty)
@@ -70,7 +77,7 @@ struct Lattice {           // device pointers of one potential, for all frames (
     int *stat;                   // [F][4]  distinct keys of the first attempt, probe-limit flag, sampled distinct keys, total length of the tiles' lists
     int sym;                     // 1: DenseCRF2D's symmetric kernel normalisation (rcf_crf_soft_ex), set per call by crf_infer
     int norm_pending;            // host side: the normaliser of this lattice is still to come out of its first filter pass
-    // sort build (build 3): rocPRIM's temporary storage, sized for F * E pairs
+    // sort build (RCF_CRF_BUILD_SORT): rocPRIM's temporary storage, sized for F * E pairs
     char *sort_tmp;
     size_t sort_tmp_bytes;
     // rcf_crf_soft_f32: the colour features as the caller's floats [F][N][3] (torchcrf.cu:84-85 converts rgbFeat to float
@@ -138,13 +145,15 @@ __device__ __forceinline__ long pk_buckets(const Lattice &Lt, int f) { return pk
 // fraction -- over that sweep lists of 0.6 E correspond to 88 % (+-16: 83-87.5 % and 0.56-0.59 E; +-24: 93-94.5 % and 0.78 E) -- so that the
 // build writes only what the frame's mode reads (tile mode: no per-entry bucket / CSR position, 8 of 14 bytes per entry; list walk: no
 // tile lists).  Without it, from the lists' exact total after the build.
-// tune bit 4 (RCF_CRF_SPLAT_GATHER): never; bit 5 (RCF_CRF_SPLAT_TILES): whenever the lists exist (tests).
+// RCF_CRF_SPLAT_GATHER: never; RCF_CRF_SPLAT_TILES: whenever the lists exist (tests).
 constexpr long TILE_SPLAT_NUM = 3, TILE_SPLAT_DEN = 5;
 constexpr long TILE_SPLAT_EST_PCT = 88;
-__device__ __forceinline__ bool tile_mode_known(const Lattice &Lt) { return Lt.est || (Lt.tune & (16 | 32)) || !Lt.tile_splat; }
+__device__ __forceinline__ bool tile_mode_known(const Lattice &Lt) {
+    return Lt.est || (Lt.opts & (RCF_CRF_SPLAT_GATHER | RCF_CRF_SPLAT_TILES)) || !Lt.tile_splat;
+}
 __device__ __forceinline__ bool tile_mode(const Lattice &Lt, int f) {
-    if (!Lt.tile_splat || (Lt.tune & 16)) return false;
-    if (Lt.tune & 32) return true;
+    if (!Lt.tile_splat || (Lt.opts & RCF_CRF_SPLAT_GATHER)) return false;
+    if (Lt.opts & RCF_CRF_SPLAT_TILES) return true;
     if (Lt.est) return (long)Lt.stat[4 * f + 2] * 100 <= TILE_SPLAT_EST_PCT * ((long)PK_SAMPLES * 256 * (Lt.pd + 1));
     return (long)Lt.stat[4 * f + 3] * TILE_SPLAT_DEN <= TILE_SPLAT_NUM * Lt.E;
 }
@@ -158,6 +167,16 @@ __device__ __forceinline__ long widx(const Lattice &Lt, int f, int r, int p) {
 // ... for thread t of the workgroup that owns tile `tile` (pixel p): no divisions
 __device__ __forceinline__ long widx_tile(const Lattice &Lt, int f, int tile, int r, int t, int p) {
     return (long)f * Lt.Ep + (Lt.wtile ? ((long)tile * (Lt.pd + 1) + r) * 256 + t : (long)r * Lt.N + p);
+}
+// the pixel that thread threadIdx.x of a 256-thread workgroup owns in 16 x 16 tile `tile` of a W x H frame: whether it lies inside
+// the frame, and its index p (0 outside)
+__device__ __forceinline__ bool tile_pixel(unsigned tile, int W, int H, int &p) {
+    const int tiles_x = (W + 15) >> 4;
+    const int ty = tile / tiles_x, tx = tile - ty * tiles_x;
+    const int py = ty * 16 + (threadIdx.x >> 4), px = tx * 16 + (threadIdx.x & 15);
+    const bool live = py < H && px < W;
+    p = live ? py * W + px : 0;
+    return live;
 }
 
 __device__ __forceinline__ unsigned key_hash(const short *key, int pd) {
@@ -247,10 +266,11 @@ __device__ __forceinline__ void lattice_key(int pd, int r, const int (&rem0)[PD_
     }
 }
 
-template <int PD>      // 2 / 5: the key arithmetic unrolls with a compile-time dimension; 0: Lt.pd at run time
+// Kernels templated on the lattice dimension (PD = Lt.pd: 2 or 5, see with_pd): the key arithmetic unrolls
+template <int PD>
 __global__ void __launch_bounds__(256) lattice_keys_kernel(Lattice Lt, const uint8_t *__restrict__ rgb, int W, int H,
                                                            float posdev, float featdev) {
-    const int pd = PD ? PD : Lt.pd;
+    constexpr int pd = PD;
     const int p = blockIdx.x * blockDim.x + threadIdx.x;
     const int f = blockIdx.y;
     if (p >= Lt.N) return;
@@ -295,7 +315,6 @@ __device__ __forceinline__ int run_tail(bool tail, int lane) {
     }
     return t;
 }
-__device__ __forceinline__ long entry_of(long idx, int, int) { return idx; }
 
 // ---------------------------------------------------------------------------------- build: insert
 __global__ void __launch_bounds__(256) lattice_insert_kernel(Lattice Lt) {
@@ -303,7 +322,7 @@ __global__ void __launch_bounds__(256) lattice_insert_kernel(Lattice Lt) {
     const int f = blockIdx.y;
     const int lane = threadIdx.x & 63;
     const bool live = idx < Lt.E;
-    const long e = live ? entry_of(idx, Lt.N, Lt.pd + 1) : 0;
+    const long e = live ? idx : 0;
     const uint4 *keys = Lt.keys + (long)f * Lt.E;
     int *entries = Lt.entries + (long)f * 2 * Lt.E;
     uint4 mine = live ? keys[e] : make_uint4(0xffffffffu, 0xffffffffu, 0xffffffffu, (unsigned)lane);
@@ -359,49 +378,70 @@ __device__ __forceinline__ int block_exclusive_scan(int v, int *total) {
     return off + inc - v;
 }
 
+// The exclusive scans of the builds are three kernels each: a `local` kernel scans the SCAN_TILE values of every workgroup
+// (scan_items) and stores the tiles' totals, scan_blocks_kernel turns the totals into the tiles' offsets, an `apply` kernel adds
+// them.  The local / apply kernels differ in what they load and store; the middle one is shared.
+// v: the thread's SCAN_ITEMS consecutive values -> ex: their exclusive prefixes inside the workgroup's tile; returns the tile's total
+__device__ __forceinline__ int scan_items(const int (&v)[SCAN_ITEMS], int (&ex)[SCAN_ITEMS]) {
+    int s = 0;
+#pragma unroll
+    for (int i = 0; i < SCAN_ITEMS; i++) s += v[i];
+    int total;
+    int off = block_exclusive_scan(s, &total);
+#pragma unroll
+    for (int i = 0; i < SCAN_ITEMS; i++) {
+        ex[i] = off;
+        off += v[i];
+    }
+    return total;
+}
+// blocksum: per frame (stride fstride) nseq sequences of nblk tile totals, nblk + 1 apart -> their exclusive prefixes, in place;
+// total (optional): [F] <- the sum of the frame's FIRST sequence.  One workgroup per frame; a sequence of more than SCAN_BLOCK
+// totals is scanned in pieces that hand a carry on.
+__global__ void __launch_bounds__(SCAN_BLOCK) scan_blocks_kernel(int *__restrict__ blocksum, long fstride, int nblk, int nseq,
+                                                                 int *__restrict__ total) {
+    const int f = blockIdx.x;
+    __shared__ int carry_s;
+    for (int which = 0; which < nseq; which++) {
+        int *bs = blocksum + (long)f * fstride + (long)which * (nblk + 1);
+        if (threadIdx.x == 0) carry_s = 0;
+        __syncthreads();
+        for (int b0 = 0; b0 < nblk; b0 += SCAN_BLOCK) {
+            const int b = b0 + threadIdx.x;
+            const int v = b < nblk ? bs[b] : 0;
+            int sum;
+            const int ex = block_exclusive_scan(v, &sum);
+            const int carry = carry_s;
+            if (b < nblk) bs[b] = carry + ex;
+            __syncthreads();
+            if (threadIdx.x == 0) carry_s = carry + sum;
+            __syncthreads();
+        }
+        if (threadIdx.x == 0 && which == 0 && total) total[f] = carry_s;
+        __syncthreads();
+    }
+}
+
 // flag[e] = entry e is the representative of its bucket; local exclusive scan + block totals
 __global__ void __launch_bounds__(SCAN_BLOCK) lattice_scan_local_kernel(Lattice Lt) {
     const int f = blockIdx.y;
     const long base = (long)blockIdx.x * SCAN_TILE + (long)threadIdx.x * SCAN_ITEMS;
     const int *bucket = Lt.vid + (long)f * Lt.E;
     const int *entries = Lt.entries + (long)f * 2 * Lt.E;
-    int flags[SCAN_ITEMS], s = 0;
+    int flags[SCAN_ITEMS], off[SCAN_ITEMS];
 #pragma unroll
     for (int i = 0; i < SCAN_ITEMS; i++) {
         const long e = base + i;
         flags[i] = (e < Lt.E && entries[bucket[e]] == (int)e) ? 1 : 0;
-        s += flags[i];
     }
-    int total;
-    int off = block_exclusive_scan(s, &total);
+    const int total = scan_items(flags, off);
     int *out = Lt.slot_vid + (long)f * Lt.E;
 #pragma unroll
     for (int i = 0; i < SCAN_ITEMS; i++) {
         const long e = base + i;
-        if (e < Lt.E) out[e] = flags[i] ? off : -1;
-        off += flags[i];
+        if (e < Lt.E) out[e] = flags[i] ? off[i] : -1;
     }
     if (threadIdx.x == 0) Lt.blocksum[(long)f * (gridDim.x + 1) + blockIdx.x] = total;
-}
-
-__global__ void __launch_bounds__(SCAN_BLOCK) lattice_scan_blocks_kernel(Lattice Lt, int nblk) {
-    const int f = blockIdx.x;
-    int *bs = Lt.blocksum + (long)f * (nblk + 1);
-    __shared__ int carry_s;
-    if (threadIdx.x == 0) carry_s = 0;
-    __syncthreads();
-    for (int b0 = 0; b0 < nblk; b0 += SCAN_BLOCK) {
-        const int b = b0 + threadIdx.x;
-        const int v = b < nblk ? bs[b] : 0;
-        int total;
-        const int ex = block_exclusive_scan(v, &total);
-        const int carry = carry_s;
-        if (b < nblk) bs[b] = carry + ex;
-        __syncthreads();
-        if (threadIdx.x == 0) carry_s = carry + total;
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) { bs[nblk] = carry_s; Lt.L[f] = carry_s; }
 }
 
 // slot_vid += block offset; vrep[vid] = slot; entry -> dense vertex id is resolved in the next kernel
@@ -483,7 +523,7 @@ __global__ void __launch_bounds__(256) csr_count_kernel(Lattice Lt) {
     const int lane = threadIdx.x & 63;
     const bool live = idx < Lt.E;
     const long fb = (long)f * Lt.E;
-    const int v = live ? Lt.vid[fb + entry_of(idx, Lt.N, Lt.pd + 1)] : -1 - lane;
+    const int v = live ? Lt.vid[fb + idx] : -1 - lane;
     const int vp = __shfl_up(v, 1, 64), vn = __shfl_down(v, 1, 64);
     const bool head = lane == 0 || vp != v, tail = lane == 63 || vn != v;
     const int seg = run_head(head, lane);
@@ -494,39 +534,15 @@ __global__ void __launch_bounds__(SCAN_BLOCK) csr_scan_local_kernel(Lattice Lt) 
     const int f = blockIdx.y;
     const long base = (long)blockIdx.x * SCAN_TILE + (long)threadIdx.x * SCAN_ITEMS;
     const int *cnt = Lt.cnt + (long)f * Lt.E;
-    int v[SCAN_ITEMS], s = 0;
+    int v[SCAN_ITEMS], off[SCAN_ITEMS];
 #pragma unroll
-    for (int i = 0; i < SCAN_ITEMS; i++) {
-        v[i] = (base + i < Lt.E) ? cnt[base + i] : 0;
-        s += v[i];
-    }
-    int total;
-    int off = block_exclusive_scan(s, &total);
+    for (int i = 0; i < SCAN_ITEMS; i++) v[i] = (base + i < Lt.E) ? cnt[base + i] : 0;
+    const int total = scan_items(v, off);
     int *out = Lt.off + (long)f * Lt.E;
 #pragma unroll
-    for (int i = 0; i < SCAN_ITEMS; i++) {
-        if (base + i < Lt.E) out[base + i] = off;
-        off += v[i];
-    }
+    for (int i = 0; i < SCAN_ITEMS; i++)
+        if (base + i < Lt.E) out[base + i] = off[i];
     if (threadIdx.x == 0) Lt.blocksum[(long)f * (gridDim.x + 1) + blockIdx.x] = total;
-}
-__global__ void __launch_bounds__(SCAN_BLOCK) csr_scan_blocks_kernel(Lattice Lt, int nblk) {
-    const int f = blockIdx.x;
-    int *bs = Lt.blocksum + (long)f * (nblk + 1);
-    __shared__ int carry_s;
-    if (threadIdx.x == 0) carry_s = 0;
-    __syncthreads();
-    for (int b0 = 0; b0 < nblk; b0 += SCAN_BLOCK) {
-        const int b = b0 + threadIdx.x;
-        const int v = b < nblk ? bs[b] : 0;
-        int total;
-        const int ex = block_exclusive_scan(v, &total);
-        const int carry = carry_s;
-        if (b < nblk) bs[b] = carry + ex;
-        __syncthreads();
-        if (threadIdx.x == 0) carry_s = carry + total;
-        __syncthreads();
-    }
 }
 // off += block offset; cnt is reset to serve as the fill cursor
 __global__ void __launch_bounds__(SCAN_BLOCK) csr_scan_apply_kernel(Lattice Lt) {
@@ -544,7 +560,7 @@ __global__ void __launch_bounds__(256) csr_fill_kernel(Lattice Lt) {
     const int lane = threadIdx.x & 63;
     const bool live = idx < Lt.E;
     const long fb = (long)f * Lt.E;
-    const long e = live ? entry_of(idx, Lt.N, Lt.pd + 1) : 0;
+    const long e = live ? idx : 0;
     const int v = live ? Lt.vid[fb + e] : -1 - lane;
     const int vp = __shfl_up(v, 1, 64), vn = __shfl_down(v, 1, 64);
     const bool head = lane == 0 || vp != v, tail = lane == 63 || vn != v;
@@ -601,13 +617,25 @@ __global__ void __launch_bounds__(256) pk_clear_kernel(Lattice Lt, int phase) {
     }
 }
 
+// the workgroup's de-duplication: `key` goes into the LDS table lkey[LT_SLOTS] (all PK_EMPTY at first) unless it is there already;
+// h: its slot.  Returns whether this thread was the one to insert it.
+__device__ __forceinline__ bool lds_insert(unsigned long long *lkey, const short *key, int pd, unsigned &h) {
+    const unsigned long long k = pack64(key, pd);
+    h = key_hash(key, pd) & (LT_SLOTS - 1);
+    for (;;) {
+        const unsigned long long prev = atomicCAS(&lkey[h], PK_EMPTY, k);
+        if (prev == PK_EMPTY || prev == k) return prev == PK_EMPTY;
+        h = (h + 1) & (LT_SLOTS - 1);
+    }
+}
+
 // distinct keys of PK_SAMPLES sampled pixel blocks (block-local de-duplication only) -> stat[4 f + 2]
-template <int PD>      // 2 / 5: the key arithmetic unrolls with a compile-time dimension; 0: Lt.pd at run time
+template <int PD>
 __global__ void __launch_bounds__(256) pk_estimate_kernel(Lattice Lt, const uint8_t *__restrict__ rgb, int W, float posdev,
                                                           float featdev) {
     __shared__ unsigned long long lkey[LT_SLOTS];
     __shared__ int distinct;
-    const int pd = PD ? PD : Lt.pd, nax = pd + 1;
+    constexpr int pd = PD, nax = PD + 1;
     const int f = blockIdx.y;
     const int nblk = (Lt.N + 255) / 256;
     const int blk = (int)(((long)blockIdx.x * nblk) / gridDim.x);
@@ -623,14 +651,8 @@ __global__ void __launch_bounds__(256) pk_estimate_kernel(Lattice Lt, const uint
         for (int r = 0; r < nax; r++) {
             short key[PD_MAX];
             lattice_key(pd, r, rem0, rank, key);
-            const unsigned long long k = pack64(key, pd);
-            unsigned h = key_hash(key, pd) & (LT_SLOTS - 1);
-            for (;;) {
-                const unsigned long long prev = atomicCAS(&lkey[h], PK_EMPTY, k);
-                if (prev == PK_EMPTY) ++mine;
-                if (prev == PK_EMPTY || prev == k) break;
-                h = (h + 1) & (LT_SLOTS - 1);
-            }
+            unsigned h;
+            if (lds_insert(lkey, key, pd, h)) ++mine;
         }
     }
     if (mine) atomicAdd(&distinct, mine);
@@ -638,13 +660,13 @@ __global__ void __launch_bounds__(256) pk_estimate_kernel(Lattice Lt, const uint
     if (threadIdx.x == 0) atomicAdd(Lt.stat + 4 * f + 2, distinct);
 }
 
-template <int PD>      // 2 / 5: the key arithmetic unrolls with a compile-time dimension; 0: Lt.pd at run time
+template <int PD>
 __global__ void __launch_bounds__(256) lattice_build_packed_kernel(Lattice Lt, const uint8_t *__restrict__ rgb, int W,
                                                                    int H, float posdev, float featdev, int phase) {
     __shared__ unsigned long long lkey[LT_SLOTS];
     __shared__ unsigned lcnt[LT_SLOTS], lgs[LT_SLOTS], lbase[LT_SLOTS];
     __shared__ int newkeys, skip, ntile;
-    const int pd = PD ? PD : Lt.pd, nax = pd + 1;
+    constexpr int pd = PD, nax = PD + 1;
     const int f = blockIdx.x;                             // frame fastest: with 8 frames per call a frame's workgroups share one XCD
     const long cap0 = pk_cap(Lt, f);
     const bool small = phase == 0 && cap0 < 2 * Lt.E;                    // an attempt that may overflow
@@ -668,11 +690,8 @@ __global__ void __launch_bounds__(256) lattice_build_packed_kernel(Lattice Lt, c
     // A workgroup takes a 16 x 16 pixel tile, not 256 pixels of one row: neighbours in BOTH directions share lattice
     // vertices, so the tile's 1 536 entries collapse to fewer distinct keys and fewer of them go to the global table
     // (the global inserts -- dependent device-scope atomics -- are what this kernel waits for).
-    const int tiles_x = (W + 15) >> 4;
-    const int ty = tile / tiles_x, tx = tile - ty * tiles_x;
-    const int py = ty * 16 + (threadIdx.x >> 4), px = tx * 16 + (threadIdx.x & 15);
-    const bool live = py < H && px < W;
-    const int p = live ? py * W + px : 0;
+    int p;
+    const bool live = tile_pixel(tile, W, H, p);
     for (int i = threadIdx.x; i < LT_SLOTS; i += blockDim.x) { lkey[i] = PK_EMPTY; lcnt[i] = 0u; }
     __syncthreads();
     float wgt[PD_MAX + 1];
@@ -684,13 +703,8 @@ __global__ void __launch_bounds__(256) lattice_build_packed_kernel(Lattice Lt, c
         for (int r = 0; r < nax; r++) {
             short key[PD_MAX];
             lattice_key(pd, r, rem0, rank, key);
-            const unsigned long long k = pack64(key, pd);
-            unsigned h = key_hash(key, pd) & (LT_SLOTS - 1);
-            for (;;) {
-                const unsigned long long prev = atomicCAS(&lkey[h], PK_EMPTY, k);
-                if (prev == PK_EMPTY || prev == k) break;
-                h = (h + 1) & (LT_SLOTS - 1);
-            }
+            unsigned h;
+            lds_insert(lkey, key, pd, h);
             lh[r] = (int)h;
             lrank[r] = (int)atomicAdd(&lcnt[h], 1u);
             wgt[r] = bary[r];
@@ -809,55 +823,27 @@ __global__ void __launch_bounds__(SCAN_BLOCK) pk_scan_local_kernel(Lattice Lt, i
             continue;
         }
         const long base = (long)vb * SCAN_TILE + (long)threadIdx.x * SCAN_ITEMS;
-        int fl[SCAN_ITEMS], cn[SCAN_ITEMS], sf = 0, sc = 0;
+        int fl[SCAN_ITEMS], cn[SCAN_ITEMS], of[SCAN_ITEMS], oc[SCAN_ITEMS];
 #pragma unroll
         for (int i = 0; i < SCAN_ITEMS; i++) {
             const long b = base + i;
             const unsigned long long cu = (b < S) ? cursor[b] : 0ull;
             cn[i] = tile ? (int)(cu >> 32) : (int)(unsigned)cu;
             fl[i] = cu != 0ull ? 1 : 0;             // every inserted key counted at least one entry
-            sf += fl[i];
-            sc += cn[i];
         }
-        int tf, tc;
-        int of = block_exclusive_scan(sf, &tf);
-        int oc = block_exclusive_scan(sc, &tc);
+        const int tf = scan_items(fl, of), tc = scan_items(cn, oc);
 #pragma unroll
         for (int i = 0; i < SCAN_ITEMS; i++) {
             const long b = base + i;
             if (b < S) {
-                sv[b] = fl[i] ? of : -1;
-                if (fl[i]) so[b] = oc;              // offsets are only ever read for occupied buckets
+                sv[b] = fl[i] ? of[i] : -1;
+                if (fl[i]) so[b] = oc[i];           // offsets are only ever read for occupied buckets
             }
-            of += fl[i];
-            oc += cn[i];
         }
         if (threadIdx.x == 0) {
             bs[vb] = tf;
             bs[nblk + 1 + vb] = tc;
         }
-    }
-}
-__global__ void __launch_bounds__(SCAN_BLOCK) pk_scan_blocks_kernel(Lattice Lt, int nblk) {
-    const int f = blockIdx.x;
-    __shared__ int carry_s;
-    for (int which = 0; which < 2; which++) {
-        int *bs = Lt.blocksum2 + (long)f * 2 * (nblk + 1) + which * (nblk + 1);
-        if (threadIdx.x == 0) carry_s = 0;
-        __syncthreads();
-        for (int b0 = 0; b0 < nblk; b0 += SCAN_BLOCK) {
-            const int b = b0 + threadIdx.x;
-            const int v = b < nblk ? bs[b] : 0;
-            int total;
-            const int ex = block_exclusive_scan(v, &total);
-            const int carry = carry_s;
-            if (b < nblk) bs[b] = carry + ex;
-            __syncthreads();
-            if (threadIdx.x == 0) carry_s = carry + total;
-            __syncthreads();
-        }
-        if (threadIdx.x == 0 && which == 0) Lt.L[f] = carry_s;
-        __syncthreads();
     }
 }
 __global__ void __launch_bounds__(SCAN_BLOCK) pk_scan_apply_kernel(Lattice Lt, int nblk) {
@@ -924,10 +910,10 @@ __global__ void __launch_bounds__(256) tile_list_kernel(Lattice Lt) {
         }
     }
 }
-template <int PD>      // 2 / 5: the key arithmetic unrolls with a compile-time dimension; 0: Lt.pd at run time
+template <int PD>
 __global__ void __launch_bounds__(256) pk_neighbours_kernel(Lattice Lt) {
     const int f = blockIdx.x;
-    const int pd = PD ? PD : Lt.pd, nax = pd + 1;
+    constexpr int pd = PD, nax = PD + 1;
     const long Lf = Lt.L[f], S = 2 * Lt.E;
     const unsigned long long *table = Lt.table + (long)f * S;
     const int *sv = Lt.slot_vid2 + (long)f * S;
@@ -960,7 +946,7 @@ __global__ void __launch_bounds__(256) pk_neighbours_kernel(Lattice Lt) {
 }
 
 // ---------------------------------------------------------------------------------- sort build
-// RCF_CRF_BUILD_SORT (build 3): the lattice by SORTING instead of hashing.  Every (pixel, remainder) entry of every frame of
+// RCF_CRF_BUILD_SORT: the lattice by SORTING instead of hashing.  Every (pixel, remainder) entry of every frame of
 // the call becomes a 64-bit key (frame << 60 | packed lattice key) with its entry index as the value; one device-wide radix sort
 // (rocPRIM) puts a frame's entries in key order, i.e. grouped by vertex: the sorted sequence IS the CSR list, run heads are the
 // vertices, an inclusive scan numbers them.  Vertices come out numbered in KEY order, which is what makes this build worth its
@@ -975,7 +961,7 @@ constexpr unsigned long long KEY60 = (1ull << 60) - 1;
 template <int PD>
 __global__ void __launch_bounds__(256) sort_keys_kernel(Lattice Lt, const uint8_t *__restrict__ rgb, int W, float posdev,
                                                         float featdev, unsigned long long *__restrict__ K, unsigned *__restrict__ V) {
-    const int pd = PD ? PD : Lt.pd;
+    constexpr int pd = PD;
     const int p = blockIdx.x * blockDim.x + threadIdx.x;
     const int f = blockIdx.y;
     if (p >= Lt.N) return;
@@ -1047,7 +1033,7 @@ __device__ __forceinline__ long lower_bound64(const unsigned long long *__restri
 template <int PD>
 __global__ void __launch_bounds__(256) sort_neighbours_coarse_kernel(Lattice Lt, const unsigned long long *__restrict__ ukey,
                                                                      int *__restrict__ coarse, int cstride) {
-    const int pd = PD ? PD : Lt.pd, nax = pd + 1;
+    constexpr int pd = PD, nax = PD + 1;
     const int f = blockIdx.x;
     const long fb = (long)f * Lt.E, Lf = Lt.L[f];
     const unsigned long long *uk = ukey + fb;
@@ -1061,7 +1047,7 @@ __global__ void __launch_bounds__(256) sort_neighbours_coarse_kernel(Lattice Lt,
 template <int PD>
 __global__ void __launch_bounds__(256) sort_neighbours_kernel(Lattice Lt, const unsigned long long *__restrict__ ukey,
                                                               const int *__restrict__ coarse, int cstride) {
-    const int pd = PD ? PD : Lt.pd, nax = pd + 1;
+    constexpr int pd = PD, nax = PD + 1;
     const int f = blockIdx.x;
     const long fb = (long)f * Lt.E, Lf = Lt.L[f];
     const unsigned long long *uk = ukey + fb;
@@ -1100,16 +1086,17 @@ constexpr int SHORT_LIST = 6;
 // MODE 0: the two label channels (Q0*w, Q1*w) -> float2.  MODE 1: the homogeneous channel (w) -> float; it does not
 // depend on Q, so it is splatted, blurred and sliced ONCE per lattice (build_lattice) instead of every iteration
 // (same operations on the same inputs as the reference's third value channel: bit-identical normalisation).
+__device__ __forceinline__ long long to_fixed(float x) { return __double2ll_rn((double)x * FIX_SCALE); }
 template <int MODE>
 __device__ __forceinline__ void acc_entry(const int2 pw, const float *__restrict__ Qf, long long &a0, long long &a1, long long &a2) {
     const float wgt = __int_as_float(pw.y);
     if (MODE == 0 || MODE == 2) {
         const float2 q = *reinterpret_cast<const float2 *>(Qf + (long)pw.x * MLAB);
-        a0 += __double2ll_rn((double)(q.x * wgt) * FIX_SCALE);
-        a1 += __double2ll_rn((double)(q.y * wgt) * FIX_SCALE);
-        if (MODE == 2) a2 += __double2ll_rn((double)wgt * FIX_SCALE);
+        a0 += to_fixed(q.x * wgt);
+        a1 += to_fixed(q.y * wgt);
+        if (MODE == 2) a2 += to_fixed(wgt);
     } else {
-        a0 += __double2ll_rn((double)wgt * FIX_SCALE);
+        a0 += to_fixed(wgt);
     }
 }
 __device__ __forceinline__ float fixed_to_float(long long a) { return (float)((double)a * (1.0 / FIX_SCALE)); }
@@ -1278,14 +1265,11 @@ __global__ void __launch_bounds__(256) splat_tile_kernel(Lattice Lt, const float
     const int f = blockIdx.x;
     if (!tile_mode(Lt, f)) return;
     const int nax = Lt.pd + 1, stride = 256 * nax;
-    const int W = Lt.W, H = Lt.N / Lt.W, tiles_x = (W + 15) >> 4;
-    const int ty = blockIdx.y / tiles_x, tx = blockIdx.y - ty * tiles_x;
-    const int py = ty * 16 + (threadIdx.x >> 4), px = tx * 16 + (threadIdx.x & 15);
+    int p;
+    const bool live = tile_pixel(blockIdx.y, Lt.W, Lt.N / Lt.W, p);
     const int n = Lt.tcnt[(long)f * Lt.tiles + blockIdx.y];
     const int R = tile_copies(n, stride);
     const int rep = tile_copy_of(threadIdx.x, R);
-    const bool live = py < H && px < W;
-    const int p = live ? py * W + px : 0;
     // everything the pixel reads from memory is asked for before the first barrier
     float wr[PD_MAX + 1];
     int sr[PD_MAX + 1];
@@ -1313,11 +1297,11 @@ __global__ void __launch_bounds__(256) splat_tile_kernel(Lattice Lt, const float
             const float wgt = wr[r];
             const int s = rep * n + sr[r];
             if (MODE == 1) {
-                atomicAdd(&acc[s], (unsigned long long)__double2ll_rn((double)wgt * FIX_SCALE));
+                atomicAdd(&acc[s], (unsigned long long)to_fixed(wgt));
             } else {
-                atomicAdd(&acc[s], (unsigned long long)__double2ll_rn((double)(q.x * wgt) * FIX_SCALE));
-                atomicAdd(&acc[CAP + s], (unsigned long long)__double2ll_rn((double)(q.y * wgt) * FIX_SCALE));
-                if (MODE == 2) atomicAdd(&acc[2 * CAP + s], (unsigned long long)__double2ll_rn((double)wgt * FIX_SCALE));
+                atomicAdd(&acc[s], (unsigned long long)to_fixed(q.x * wgt));
+                atomicAdd(&acc[CAP + s], (unsigned long long)to_fixed(q.y * wgt));
+                if (MODE == 2) atomicAdd(&acc[2 * CAP + s], (unsigned long long)to_fixed(wgt));
             }
         }
     }
@@ -1421,7 +1405,7 @@ __global__ void __launch_bounds__(256) slice_norm_kernel(Lattice Lt, const float
     const int p = blockIdx.y * blockDim.x + threadIdx.x;
     if (p >= Lt.N) return;
     const long fb = (long)f * Lt.E;
-    const int pd = PD ? PD : Lt.pd;
+    constexpr int pd = PD;
     float sw = 0;
 #pragma unroll
     for (int r = 0; r <= pd; r++) {
@@ -1446,11 +1430,9 @@ __global__ void __launch_bounds__(256) slice_kernel(Lattice Lt, const float2 *__
                                                     int last, int write_map, int sym, const float *__restrict__ z = nullptr) {
     const int f = blockIdx.x;
     // 16 x 16 pixel tiles: the pixels of a tile share most of their lattice vertices (the values stay in the CU's L1)
-    const int W = Lt.W, H = Lt.N / Lt.W, tiles_x = (W + 15) >> 4;
-    const int ty = blockIdx.y / tiles_x, tx = blockIdx.y - ty * tiles_x;
-    const int py = ty * 16 + (threadIdx.x >> 4), px = tx * 16 + (threadIdx.x & 15);
-    const int nax = (PD ? PD : Lt.pd) + 1;
-    constexpr int NAXC = PD ? PD + 1 : PD_MAX + 1;        // compile-time loop bound (PD = 0: guarded by nax)
+    int p;
+    const bool live = tile_pixel(blockIdx.y, Lt.W, Lt.N / Lt.W, p);
+    constexpr int nax = PD + 1;
     const long fb = (long)f * Lt.E;
     // tile mode: the tile's distinct vertices are a short list (the build's): their values are fetched ONCE into LDS and a pixel
     // reads them by its entries' list positions (2 bytes each) instead of gathering 8 bytes per entry by vertex id
@@ -1462,8 +1444,6 @@ __global__ void __launch_bounds__(256) slice_kernel(Lattice Lt, const float2 *__
     float2 *sval = SPLAT ? reinterpret_cast<float2 *>(acc) : sval_own;
     float *szv = SPLAT ? reinterpret_cast<float *>(acc + CAP) : szv_own;
     const bool tile = tile_mode(Lt, f);                   // (uniform)
-    const bool live = py < H && px < W;
-    const int p = live ? py * W + px : 0;
     // the pixel's own streams (weights, list positions, normaliser, unary) are asked for BEFORE the tile's values are staged: they
     // depend on nothing in LDS, and behind the barrier their latency would come on top of the staging gather's
     float wr[PD_MAX + 1];
@@ -1472,8 +1452,7 @@ __global__ void __launch_bounds__(256) slice_kernel(Lattice Lt, const float2 *__
     float2 un_pre = make_float2(0.f, 0.f);
     if (tile && live) {
 #pragma unroll
-        for (int r = 0; r < NAXC; r++) {
-            if (!PD && r >= nax) break;
+        for (int r = 0; r < nax; r++) {
             const long pe = widx_tile(Lt, f, blockIdx.y, r, threadIdx.x, p);
             wr[r] = Lt.weight[pe];
             sr[r] = Lt.tslot[pe];
@@ -1499,8 +1478,7 @@ __global__ void __launch_bounds__(256) slice_kernel(Lattice Lt, const float2 *__
     if (live) {
         float s0 = 0, s1 = 0, sw = 0;
 #pragma unroll
-        for (int r = 0; r < NAXC; r++) {
-            if (!PD && r >= nax) break;
+        for (int r = 0; r < nax; r++) {
             const long pe = fb + (long)r * Lt.N + p;
             float wgt;
             float2 v;
@@ -1566,11 +1544,10 @@ __global__ void __launch_bounds__(256) slice_kernel(Lattice Lt, const float2 *__
         if (have_q) {
             const int rep = tile_copy_of(threadIdx.x, R);
 #pragma unroll
-            for (int r = 0; r < NAXC; r++) {
-                if (!PD && r >= nax) break;
+            for (int r = 0; r < nax; r++) {
                 const int sl = rep * n + sr[r];
-                atomicAdd(&acc[sl], (unsigned long long)__double2ll_rn((double)(qs0 * wr[r]) * FIX_SCALE));
-                atomicAdd(&acc[CAP + sl], (unsigned long long)__double2ll_rn((double)(qs1 * wr[r]) * FIX_SCALE));
+                atomicAdd(&acc[sl], (unsigned long long)to_fixed(qs0 * wr[r]));
+                atomicAdd(&acc[CAP + sl], (unsigned long long)to_fixed(qs1 * wr[r]));
             }
         }
         __syncthreads();
@@ -1726,7 +1703,9 @@ struct Carver {
 
 inline int scan_blocks(long E) { return (int)((E + SCAN_TILE - 1) / SCAN_TILE); }
 
-void carve_lattice(Carver &c, Lattice &L, int pd, int N, int F, int W) {
+template <int pd>
+void carve_lattice(Carver &c, Lattice &L, int N, int F, int W) {
+    static_assert(pd == 2 || pd == 5, "the kernels templated on the dimension are instantiated for these two (with_pd)");
     L.pd = pd;
     L.N = N;
     L.W = W;
@@ -1778,8 +1757,8 @@ struct CrfBuffers {
 size_t carve_all(char *base, int W, int H, int F, CrfBuffers &b) {
     Carver c{base, 0};
     const int N = W * H;
-    carve_lattice(c, b.smooth, 2, N, F, W);
-    carve_lattice(c, b.app, 5, N, F, W);
+    carve_lattice<2>(c, b.smooth, N, F, W);
+    carve_lattice<5>(c, b.app, N, F, W);
     b.cur = c.take<float>((size_t)F * N * MLAB);
     b.next = c.take<float>((size_t)F * N * MLAB);
     b.unary_own = c.take<float>((size_t)F * N * MLAB);
@@ -1795,13 +1774,15 @@ size_t carve_all(char *base, int W, int H, int F, CrfBuffers &b) {
 int build_lattice_norm(Lattice &L, int F, hipStream_t st);
 int lattice_built(Lattice &L, int F, hipStream_t st);
 
-// kernels templated on the lattice dimension: the two potentials of the reference are pd = 2 and pd = 5
-#define PD_LAUNCH(pd_, kern, grid, block, st_, ...)                                              \
-    do {                                                                                        \
-        if ((pd_) == 5) hipLaunchKernelGGL(kern<5>, grid, block, 0, st_, __VA_ARGS__);          \
-        else if ((pd_) == 2) hipLaunchKernelGGL(kern<2>, grid, block, 0, st_, __VA_ARGS__);     \
-        else hipLaunchKernelGGL(kern<0>, grid, block, 0, st_, __VA_ARGS__);                     \
-    } while (0)
+// kernels templated on the lattice dimension: the two potentials of the reference are pd = 5 (appearance) and pd = 2 (position),
+// and carve_lattice makes no other.  with_pd(pd, [&](auto PD) { ... kern<PD()> ... }) runs its body with pd as a constant.
+template <class Body>
+void with_pd(int pd, Body &&body) {
+    if (pd == 5) body(std::integral_constant<int, 5>());
+    else body(std::integral_constant<int, 2>());
+}
+#define PD_LAUNCH(pd_, kern, grid, block, st_, ...) \
+    with_pd(pd_, [&](auto PD) { hipLaunchKernelGGL(kern<PD()>, grid, block, 0, st_, __VA_ARGS__); })
 
 // bound on |key coordinate| (see lattice_point): elevated[i] in [-i*cf_i, sum_j cf_j], keys within pd+1 of it
 bool keys_fit_12bit(int pd, int W, int H, float posdev, float featdev) {
@@ -1822,12 +1803,12 @@ int build_lattice_packed(Lattice &L, const uint8_t *rgb, int W, int H, int F, fl
     const dim3 gpf(F, rcf_cdiv(W, 16) * rcf_cdiv(H, 16));        // (frames, 16 x 16 pixel tiles)
     const int nblk2 = scan_blocks(2 * L.E);
     // first attempt: 2^18 - 1 buckets (3 MB of keys + cursors per frame, room for 131 k distinct keys; measured at
-    // 480x854, T=5: 2^21 0.388, 2^19 0.371, 2^18 0.361 ms/frame); L.build 2 forces a tiny table (tests)
-    const long small = L.build == 2 ? 1021 : ((1L << 18) - 1);
+    // 480x854, T=5: 2^21 0.388, 2^19 0.371, 2^18 0.361 ms/frame); RCF_CRF_BUILD_SMALL_TABLE forces a tiny table (tests)
+    const long small = L.build == RCF_CRF_BUILD_SMALL_TABLE ? 1021 : ((1L << 18) - 1);
     L.cap_small = (int)(small < 2 * L.E ? small : 2 * L.E);
     L.tile_splat = 1;                                            // every kernel below sees it (the struct travels by value)
     L.wtile = 1;
-    L.est = (L.build != 2 && L.cap_small < 2 * L.E && rcf_cdiv(L.N, 256) >= 4 * PK_SAMPLES) ? 1 : 0;
+    L.est = (L.build != RCF_CRF_BUILD_SMALL_TABLE && L.cap_small < 2 * L.E && rcf_cdiv(L.N, 256) >= 4 * PK_SAMPLES) ? 1 : 0;
     hipLaunchKernelGGL(pk_stat_reset_kernel, dim3(1), dim3(64), 0, st, L, F);
     if (L.est) PD_LAUNCH(L.pd, pk_estimate_kernel, dim3(PK_SAMPLES, F), dim3(256), st, L, rgb, W, posdev, featdev);
     hipLaunchKernelGGL(pk_clear_kernel, dim3(F, 256), dim3(256), 0, st, L, 0);
@@ -1840,7 +1821,7 @@ int build_lattice_packed(Lattice &L, const uint8_t *rgb, int W, int H, int F, fl
     }
     const int gscan = nblk2 < 256 ? nblk2 : 256;
     hipLaunchKernelGGL(pk_scan_local_kernel, dim3(gscan, F), dim3(SCAN_BLOCK), 0, st, L, nblk2);
-    hipLaunchKernelGGL(pk_scan_blocks_kernel, dim3(F), dim3(SCAN_BLOCK), 0, st, L, nblk2);
+    hipLaunchKernelGGL(scan_blocks_kernel, dim3(F), dim3(SCAN_BLOCK), 0, st, L.blocksum2, 2L * (nblk2 + 1), nblk2, 2, L.L);
     hipLaunchKernelGGL(pk_scan_apply_kernel, dim3(gscan, F), dim3(SCAN_BLOCK), 0, st, L, nblk2);
     hipLaunchKernelGGL(pk_fill_kernel, dim3(F, 2048), dim3(256), 0, st, L);        // (returns at once on tile-mode frames)
     hipLaunchKernelGGL(tile_list_kernel, dim3(F, L.tiles), dim3(256), 0, st, L);      // one workgroup per tile: two dependent gathers per entry
@@ -1886,10 +1867,10 @@ int build_lattice(Lattice &L, const uint8_t *rgb, int W, int H, int F, float pos
     L.wtile = 0;                                                 // ... and stores the weights tile-major
     const dim3 gp(rcf_cdiv(L.N, 256), F), ge(rcf_cdiv(L.E, 256), F);
     const int nblk = scan_blocks(L.E);
-    if (L.build != 1 && keys_fit_12bit(L.pd, W, H, posdev, featdev)) {
+    if (L.build != RCF_CRF_BUILD_ARRAY && keys_fit_12bit(L.pd, W, H, posdev, featdev)) {
         // the sort build for the appearance lattice only (the position lattice has a few hundred vertices whatever the frame
         // shows); 60 key bits + up to 4 frame bits
-        if (L.build == 3 && L.pd == 5 && F <= 16) {
+        if (L.build == RCF_CRF_BUILD_SORT && L.pd == 5 && F <= 16) {
             if (int e = build_lattice_sorted(L, rgb, W, H, F, posdev, featdev, st)) return e;
         } else if (int e = build_lattice_packed(L, rgb, W, H, F, posdev, featdev, st)) {
             return e;
@@ -1900,7 +1881,7 @@ int build_lattice(Lattice &L, const uint8_t *rgb, int W, int H, int F, float pos
     PD_LAUNCH(L.pd, lattice_keys_kernel, gp, dim3(256), st, L, rgb, W, H, posdev, featdev);
     hipLaunchKernelGGL(lattice_insert_kernel, ge, dim3(256), 0, st, L);
     hipLaunchKernelGGL(lattice_scan_local_kernel, dim3(nblk, F), dim3(SCAN_BLOCK), 0, st, L);
-    hipLaunchKernelGGL(lattice_scan_blocks_kernel, dim3(F), dim3(SCAN_BLOCK), 0, st, L, nblk);
+    hipLaunchKernelGGL(scan_blocks_kernel, dim3(F), dim3(SCAN_BLOCK), 0, st, L.blocksum, nblk + 1L, nblk, 1, L.L);
     hipLaunchKernelGGL(lattice_scan_apply_kernel, dim3(nblk, F), dim3(SCAN_BLOCK), 0, st, L);
     hipLaunchKernelGGL(lattice_entry_vid_kernel, ge, dim3(256), 0, st, L);
     hipLaunchKernelGGL(neighbours_init_kernel, dim3(2048, F), dim3(256), 0, st, L);
@@ -1908,7 +1889,7 @@ int build_lattice(Lattice &L, const uint8_t *rgb, int W, int H, int F, float pos
     CK(hipMemsetAsync(L.cnt, 0, (size_t)F * L.E * sizeof(int), st));
     hipLaunchKernelGGL(csr_count_kernel, ge, dim3(256), 0, st, L);
     hipLaunchKernelGGL(csr_scan_local_kernel, dim3(nblk, F), dim3(SCAN_BLOCK), 0, st, L);
-    hipLaunchKernelGGL(csr_scan_blocks_kernel, dim3(F), dim3(SCAN_BLOCK), 0, st, L, nblk);
+    hipLaunchKernelGGL(scan_blocks_kernel, dim3(F), dim3(SCAN_BLOCK), 0, st, L.blocksum, nblk + 1L, nblk, 1, (int *)nullptr);
     hipLaunchKernelGGL(csr_scan_apply_kernel, dim3(nblk, F), dim3(SCAN_BLOCK), 0, st, L);
     hipLaunchKernelGGL(csr_fill_kernel, ge, dim3(256), 0, st, L);
     RCF_LAUNCH_CHECK();
@@ -1924,12 +1905,15 @@ int lattice_built(Lattice &L, int F, hipStream_t st) {
     return 0;
 }
 
+// workgroups per frame of the vertex kernels (the blurs).  The splat's vertex pass has its own figure: launch_splat.
+constexpr int VERTEX_GRID = 1024;
+
 // the splat of one filter pass: the per-tile sums of the frames in tile mode (the kernel returns at once on the others), then the
 // vertex pass -- the list walk over the entries, or the sum of a vertex's few per-tile partial sums
 template <int MODE>
 void launch_splat(Lattice &L, int F, const float *Q, void *out, float *outz, hipStream_t st, bool tiles_done = false) {
     // tiles_done: the previous pass's slice already summed this pass's marginals per tile (slice_kernel SPLAT)
-    if (L.tile_splat && !(L.tune & 16) && !tiles_done) hipLaunchKernelGGL(splat_tile_kernel<MODE>, dim3(F, L.tiles), dim3(256), 0, st, L, Q);
+    if (L.tile_splat && !(L.opts & RCF_CRF_SPLAT_GATHER) && !tiles_done) hipLaunchKernelGGL(splat_tile_kernel<MODE>, dim3(F, L.tiles), dim3(256), 0, st, L, Q);
     // (frames, 768): measured over 256 ... 4096 workgroups per frame -- the list walk of natural frames 233 us per pass of 8 frames
     // against 240 at 4096, the tile-mode vertex pass 154 against 162 (a few 10^4 vertices per frame: most of 4096 x 256 lanes only
     // start and stop), noise frames the same at every size
@@ -1942,7 +1926,7 @@ int build_lattice_norm(Lattice &L, int F, hipStream_t st) {
     float *za = reinterpret_cast<float *>(L.val0), *zb = reinterpret_cast<float *>(L.val1);
     launch_splat<1>(L, F, nullptr, (void *)za, nullptr, st);
     for (int axis = 0; axis <= L.pd; axis++) {
-        hipLaunchKernelGGL(blur_kernel<float>, dim3(F, 1024), dim3(256), 0, st, L, axis, (const float *)za, zb);
+        hipLaunchKernelGGL(blur_kernel<float>, dim3(F, VERTEX_GRID), dim3(256), 0, st, L, axis, (const float *)za, zb);
         float *t = za; za = zb; zb = t;
     }
     PD_LAUNCH(L.pd, slice_norm_kernel, gp, dim3(256), st, L, (const float *)za, L.sym);
@@ -1952,65 +1936,54 @@ int build_lattice_norm(Lattice &L, int F, hipStream_t st) {
 }
 
 // tmp-free filter + Potts + softmax epilogue for one potential
-#define SLICE_LAUNCH(NORMv, SPLATv, zptr)                                                                                        \
-    do {                                                                                                                         \
-        if (L.pd == 5) hipLaunchKernelGGL((slice_kernel<5, NORMv, SPLATv>), gp, dim3(256), 0, st, L, (const float2 *)a, unary, next, Qout, map, first, last, write_map, L.sym, (const float *)(zptr)); \
-        else if (L.pd == 2) hipLaunchKernelGGL((slice_kernel<2, NORMv, SPLATv>), gp, dim3(256), 0, st, L, (const float2 *)a, unary, next, Qout, map, first, last, write_map, L.sym, (const float *)(zptr)); \
-        else hipLaunchKernelGGL((slice_kernel<0, NORMv, SPLATv>), gp, dim3(256), 0, st, L, (const float2 *)a, unary, next, Qout, map, first, last, write_map, L.sym, (const float *)(zptr)); \
-    } while (0)
-
 // tiles_done: this pass's per-tile sums exist already (the previous pass's slice made them); fuse_next: this pass's slice makes the
 // next pass's (single potential, not the last iteration, tile splat available: crf_infer)
 int apply_lattice(Lattice &L, int F, const float *Q, const float *unary, float *next, float *Qout, short *map,
                   int first, int last, int write_map, hipStream_t st, bool tiles_done = false, bool fuse_next = false) {
-    static const int GRIDS[8] = {1024, 256, 384, 512, 768, 2048, 128, 192};    // (L.tune >> 1) & 7: lab only
-    const dim3 gv(F, GRIDS[(L.tune >> 1) & 7]), gp(F, rcf_cdiv(L.W, 16) * rcf_cdiv(L.N / L.W, 16));     // (frames, 16 x 16 tiles): see splat_gather_kernel
-    const bool pairs = !(L.tune & 1);                          // RCF_CRF_BLUR_SEQUENTIAL: one launch per axis (tests, A/B)
+    const dim3 gv(F, VERTEX_GRID), gp(F, rcf_cdiv(L.W, 16) * rcf_cdiv(L.N / L.W, 16));     // (frames, 16 x 16 tiles): see splat_gather_kernel
+    const bool pairs = !(L.opts & RCF_CRF_BLUR_SEQUENTIAL);    // else one launch per axis (tests, A/B)
+    // the first pass after a build carries the homogeneous channel z along (lattice_built): the build's key array is dead by now,
+    // its 16 bytes per entry hold the two buffers of z (never tiles_done: the first pass of a call)
+    const bool norm = L.norm_pending != 0;
     float2 *a = L.val0, *b = L.val1;
-    if (L.norm_pending) {
-        // the build's key array is dead by now: its 16 bytes per entry hold the two homogeneous-channel buffers
-        float *za = reinterpret_cast<float *>(L.keys), *zb = za + (size_t)F * L.E;
-        launch_splat<2>(L, F, Q, (void *)a, za, st);             // (never tiles_done: the first pass of a call)
-        for (int axis = 0; axis <= L.pd; axis++) {
-            if (pairs && axis + 1 <= L.pd) {
-                hipLaunchKernelGGL(blur_pair_kernel<true>, gv, dim3(256), 0, st, L, axis, (const float2 *)a, b, (const float *)za, zb);
-                ++axis;
-            } else {
-                hipLaunchKernelGGL(blur2_kernel, gv, dim3(256), 0, st, L, axis, (const float2 *)a, b, (const float *)za, zb);
-            }
-            float2 *t = a; a = b; b = t;
-            float *tz = za; za = zb; zb = tz;
-        }
-        if (fuse_next) SLICE_LAUNCH(true, true, za);
-        else SLICE_LAUNCH(true, false, za);
-        RCF_LAUNCH_CHECK();
-        L.norm_pending = 0;
-        return 0;
-    }
-    launch_splat<0>(L, F, Q, (void *)a, nullptr, st, tiles_done);
+    float *za = norm ? reinterpret_cast<float *>(L.keys) : nullptr, *zb = norm ? za + (size_t)F * L.E : nullptr;
+    if (norm) launch_splat<2>(L, F, Q, (void *)a, za, st);
+    else launch_splat<0>(L, F, Q, (void *)a, nullptr, st, tiles_done);
     for (int axis = 0; axis <= L.pd; axis++) {
         if (pairs && axis + 1 <= L.pd) {
-            hipLaunchKernelGGL(blur_pair_kernel<false>, gv, dim3(256), 0, st, L, axis, (const float2 *)a, b, (const float *)nullptr, (float *)nullptr);
+            if (norm) hipLaunchKernelGGL(blur_pair_kernel<true>, gv, dim3(256), 0, st, L, axis, (const float2 *)a, b, (const float *)za, zb);
+            else hipLaunchKernelGGL(blur_pair_kernel<false>, gv, dim3(256), 0, st, L, axis, (const float2 *)a, b, (const float *)za, zb);
             ++axis;
+        } else if (norm) {
+            hipLaunchKernelGGL(blur2_kernel, gv, dim3(256), 0, st, L, axis, (const float2 *)a, b, (const float *)za, zb);
         } else {
             hipLaunchKernelGGL(blur_kernel<float2>, gv, dim3(256), 0, st, L, axis, (const float2 *)a, b);
         }
-        float2 *t = a; a = b; b = t;
+        std::swap(a, b);
+        std::swap(za, zb);
     }
-    if (fuse_next) SLICE_LAUNCH(false, true, nullptr);
-    else SLICE_LAUNCH(false, false, nullptr);
+#define SLICE(NORMv, SPLATv)                                                                                                      \
+    with_pd(L.pd, [&](auto PD) {                                                                                                  \
+        hipLaunchKernelGGL((slice_kernel<PD(), NORMv, SPLATv>), gp, dim3(256), 0, st, L, (const float2 *)a, unary, next, Qout, map, \
+                           first, last, write_map, L.sym, (const float *)za);                                                     \
+    })
+    if (norm && fuse_next) SLICE(true, true);
+    else if (norm) SLICE(true, false);
+    else if (fuse_next) SLICE(false, true);
+    else SLICE(false, false);
+#undef SLICE
     RCF_LAUNCH_CHECK();
+    L.norm_pending = 0;
     return 0;
 }
 
 int crf_infer(const uint8_t *rgb, const float *unary, int W, int H, int F, float scomp_smooth, float sxy_smooth,
               float scomp_app, float sxy_app, float srgb_app, int iters, int16_t *out_map, float *q_out,
-              int32_t *nvert, CrfBuffers &b, hipStream_t st, int sym = 0, int build = 0, const float *featf = nullptr) {
+              int32_t *nvert, CrfBuffers &b, hipStream_t st, int sym = 0, int opts = 0, const float *featf = nullptr) {
     b.smooth.sym = b.app.sym = sym;                                // per call, not per process: concurrent callers differ
+    b.smooth.opts = b.app.opts = opts;                             // rcf_crf_soft_ex's `normalization`: see Lattice::opts
     // float features are unbounded: the array-of-keys build (16-bit key coordinates, the reference's `short`) takes them
-    b.smooth.tune = b.app.tune = build >> 4;
-    build &= 3;
-    b.smooth.build = b.app.build = featf ? 1 : build;
+    b.smooth.build = b.app.build = featf ? RCF_CRF_BUILD_ARRAY : (opts & BUILD_FIELD);
     b.smooth.featf = b.app.featf = featf;
     const bool has_s = scomp_smooth > 0.f && sxy_smooth > 0.f;     // torchcrf.cu:28
     const bool has_a = scomp_app > 0.f && sxy_app > 0.f;           // torchcrf.cu:41
@@ -2032,9 +2005,9 @@ int crf_infer(const uint8_t *rgb, const float *unary, int W, int H, int F, float
         RCF_LAUNCH_CHECK();
     }
     // one potential: the slice of a pass hands its marginals straight to the next pass's per-tile sums (slice_kernel SPLAT) on the
-    // frames in tile mode; tune bit 6 (RCF_CRF_SLICE_SPLAT_SEPARATE): two kernels as with two potentials (tests, A/B)
+    // frames in tile mode; RCF_CRF_SLICE_SPLAT_SEPARATE: two kernels as with two potentials (tests, A/B)
     Lattice &one = has_a ? b.app : b.smooth;
-    const bool fuse = npot == 1 && one.tile_splat && !(one.tune & (16 | 64));
+    const bool fuse = npot == 1 && one.tile_splat && !(opts & (RCF_CRF_SPLAT_GATHER | RCF_CRF_SLICE_SPLAT_SEPARATE));
     for (int it = 0; it < iters; it++) {
         const int wm = (it == iters - 1) ? 1 : 0;
         const bool done = fuse && it > 0, nxt = fuse && it + 1 < iters;
@@ -2059,17 +2032,26 @@ extern "C" size_t rcf_crf_workspace_bytes(int W, int H, int batch) {
 }
 
 namespace {
-int crf_soft_impl(const uint8_t *rgb, const float *unary, int W, int H, int batch, float scomp_smooth, float sxy_smooth,
-                  float scomp_app, float sxy_app, float srgb_app, int iters, int sym, int16_t *out_map, float *q_out,
-                  int32_t *nvert, void *workspace, size_t workspace_bytes, void *stream, int build = 0,
-                  const float *featf = nullptr) {
-    if ((!rgb && !featf) || !unary || !out_map || W <= 0 || H <= 0 || batch <= 0 || iters < 0) return RCF_EINVAL;
+// what rcf_crf_hard and the rcf_crf_soft* entries share: the checks of the common arguments (ptrs: the entry's own pointers are
+// there), then the workspace carved into b
+int crf_open(bool ptrs, int W, int H, int batch, int iters, void *workspace, size_t workspace_bytes, CrfBuffers &b) {
+    if (!ptrs || W <= 0 || H <= 0 || batch <= 0 || iters < 0) return RCF_EINVAL;
     if ((long)W * H * 6 >= (1L << 30)) return RCF_EINVAL;
     if (!workspace || workspace_bytes < rcf_crf_workspace_bytes(W, H, batch) || !rcf_aligned16(workspace)) return RCF_EWORKSPACE;
-    CrfBuffers b;
     carve_all((char *)workspace, W, H, batch, b);
+    return 0;
+}
+
+// normalization: 0 / 1 in the low byte, the RCF_CRF_* switches above it (rcf_crf_soft_ex)
+int crf_soft_impl(const uint8_t *rgb, const float *unary, int W, int H, int batch, float scomp_smooth, float sxy_smooth,
+                  float scomp_app, float sxy_app, float srgb_app, int iters, int normalization, int16_t *out_map, float *q_out,
+                  int32_t *nvert, void *workspace, size_t workspace_bytes, void *stream, const float *featf = nullptr) {
+    const int sym = normalization & 0xff;
+    if (sym != 0 && sym != 1) return RCF_EINVAL;
+    CrfBuffers b;
+    if (int e = crf_open((rgb || featf) && unary && out_map, W, H, batch, iters, workspace, workspace_bytes, b)) return e;
     return crf_infer(rgb, unary, W, H, batch, scomp_smooth, sxy_smooth, scomp_app, sxy_app, srgb_app, iters, out_map,
-                     q_out, nvert, b, rcf_stream(stream), sym, build, featf);
+                     q_out, nvert, b, rcf_stream(stream), sym, normalization, featf);
 }
 }  // namespace
 
@@ -2085,43 +2067,35 @@ extern "C" int rcf_crf_soft(const uint8_t *rgb, const float *unary, int W, int H
  * (pydensecrf DenseCRF2D.addPairwiseBilateral / addPairwiseGaussian defaults, NORMALIZE_SYMMETRIC): the filter is
  * N^1/2 K N^1/2 with N = diag(1 / (K 1 + 1e-20)) instead of diag(1 / K 1) K -- what tools/pydenseCRF/crf.py:58-89 and
  * models/crf_head.py:62-91 (crf_cpu) compute.  Exactly one potential may be active in that mode.  The mode travels as a
- * parameter (no process-wide state): calls with different normalisations may run concurrently from several threads. */
+ * parameter (no process-wide state): calls with different normalisations may run concurrently from several threads.
+ * Above the low byte: the RCF_CRF_* switches of include/rcf_hip.h (lattice build, iteration variants: tests and A/B measurements,
+ * identical results); every other bit is accepted and ignored -- 11-13 once chose a grid size in the lab. */
 extern "C" int rcf_crf_soft_ex(const uint8_t *rgb, const float *unary, int W, int H, int batch, float scomp_smooth,
                                float sxy_smooth, float scomp_app, float sxy_app, float srgb_app, int iters,
                                int normalization, int16_t *out_map, float *q_out, int32_t *nvert, void *workspace,
                                size_t workspace_bytes, void *stream) {
-    // bits 8-9: lattice build (RCF_CRF_BUILD_*: tests and A/B measurements; identical results)
-    // bits 10-17: iteration variants (RCF_CRF_BLUR_SEQUENTIAL; lab grids; RCF_CRF_SPLAT_*; RCF_CRF_SLICE_SPLAT_SEPARATE) -- they
-    // travel to crf_infer above the build's two bits
-    const int build = ((normalization >> 8) & 3) | (((normalization >> 10) & 0xff) << 4);
-    normalization &= 0xff;
-    if (normalization != 0 && normalization != 1) return RCF_EINVAL;
     return crf_soft_impl(rgb, unary, W, H, batch, scomp_smooth, sxy_smooth, scomp_app, sxy_app, srgb_app, iters,
-                         normalization, out_map, q_out, nvert, workspace, workspace_bytes, stream, build);
+                         normalization, out_map, q_out, nvert, workspace, workspace_bytes, stream);
 }
 
 /* rcf_crf_soft_ex on float colour features [batch,H,W,3]: torchcrf_cpp.crf_soft converts ANY rgbFeat dtype to float without
  * rounding (tools/torchCRF/src/torchcrf.cu:84-85), so a caller with non-integer features gets the lattice of exactly those
- * values.  Always the array-of-keys build (the packed builds assume the u8 range). */
+ * values.  Always the array-of-keys build (the packed builds assume the u8 range); the RCF_CRF_* switches are ignored. */
 extern "C" int rcf_crf_soft_f32(const float *rgbf, const float *unary, int W, int H, int batch, float scomp_smooth,
                                 float sxy_smooth, float scomp_app, float sxy_app, float srgb_app, int iters,
                                 int normalization, int16_t *out_map, float *q_out, int32_t *nvert, void *workspace,
                                 size_t workspace_bytes, void *stream) {
-    normalization &= 0xff;
-    if (!rgbf || (normalization != 0 && normalization != 1)) return RCF_EINVAL;
     return crf_soft_impl(nullptr, unary, W, H, batch, scomp_smooth, sxy_smooth, scomp_app, sxy_app, srgb_app, iters,
-                         normalization, out_map, q_out, nvert, workspace, workspace_bytes, stream, 1, rgbf);
+                         normalization & 0xff, out_map, q_out, nvert, workspace, workspace_bytes, stream, rgbf);
 }
 
 extern "C" int rcf_crf_hard(const uint8_t *rgb, const int16_t *label, int W, int H, int batch, float scomp_smooth,
                             float sxy_smooth, float scomp_app, float sxy_app, float srgb_app, float confidence,
                             int iters, int16_t *out_map, float *q_out, int32_t *nvert, void *workspace,
                             size_t workspace_bytes, void *stream) {
-    if (!rgb || !label || !out_map || W <= 0 || H <= 0 || batch <= 0 || iters < 0) return RCF_EINVAL;
     if (!(confidence > 0.f && confidence < 1.f)) return RCF_EINVAL;
-    if (!workspace || workspace_bytes < rcf_crf_workspace_bytes(W, H, batch) || !rcf_aligned16(workspace)) return RCF_EWORKSPACE;
     CrfBuffers b;
-    carve_all((char *)workspace, W, H, batch, b);
+    if (int e = crf_open(rgb && label && out_map, W, H, batch, iters, workspace, workspace_bytes, b)) return e;
     hipStream_t st = rcf_stream(stream);
     const long n = (long)batch * W * H;
     // setUnaryEnergyFromLabel, densecrf_gpu.cu:84-143 (M = 2)

@@ -13,7 +13,8 @@ import torch
 import crf_oracle
 import rcf_amd
 from rcf_amd import synth
-from rcf_amd.crf import crf_soft_batched
+from rcf_amd.crf import (BLUR_SEQUENTIAL, BUILD_ARRAY, BUILD_SMALL_TABLE, BUILD_SORT, SLICE_SPLAT_SEPARATE, SPLAT_GATHER, SPLAT_TILES,
+                         crf_soft_batched)
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -90,22 +91,22 @@ def test_crf_invariants_fullsize(report):
 
 def test_crf_build_variants_identical(report):
     """the packed 64-bit-key lattice build (default; small table first, all buckets after an overflow) and the
-    array-of-keys build give the same MAP, Q and vertex count"""
+    array-of-keys build give the same MAP, Q and vertex count.  250 x 350: 525 000 entries per frame are 257 scan tiles of 2 048
+    (the last one partial) -- the smallest size at which the array-of-keys build's block sums need the carry past 256 tiles"""
     from rcf_amd import _lib, synth
-    from rcf_amd.crf import crf_soft_batched
-    H, W = 120, 214
-    head = rcf_amd.CRFHead(None, refine_iters=5)
-    imgs = torch.from_numpy(np.stack([synth.normalize_rgb(synth.smooth_rgb(H, W, 4100 + i)) for i in range(3)])).to(DEV)
-    masks = torch.from_numpy(np.stack([synth.soft_blob_mask(H, W, 4100 + i) for i in range(3)])).to(DEV)
-    rgb, unary = head.prepare(imgs, masks)
-    out = {}
-    for v in (0, 1, 2):                          # 2: a 1024-bucket first attempt, so every frame takes the overflow path
-        out[v] = crf_soft_batched(rgb, unary, W, H, 0.0, 0.0, 5.0, 60.0, 5.0, 5, want_q=True, want_nvert=True, build=v)
-    same_map = bool(torch.equal(out[0][0], out[1][0])) and bool(torch.equal(out[0][0], out[2][0]))
-    dq = max(float((out[0][1] - out[1][1]).abs().max()), float((out[0][1] - out[2][1]).abs().max()))
-    report(f"crf build variants: MAP identical {same_map}, max |dQ| {dq:.2e}, vertices {out[0][2][:, 1].tolist()} vs "
-           f"{out[1][2][:, 1].tolist()} vs {out[2][2][:, 1].tolist()} (packed / array-of-keys / packed after a table overflow)")
-    assert same_map and dq == 0.0 and torch.equal(out[0][2], out[1][2]) and torch.equal(out[0][2], out[2][2])
+    for H, W, n, iters in ((120, 214, 3, 5), (250, 350, 2, 2)):
+        head = rcf_amd.CRFHead(None, refine_iters=iters)
+        imgs = torch.from_numpy(np.stack([synth.normalize_rgb(synth.smooth_rgb(H, W, 4100 + i)) for i in range(n)])).to(DEV)
+        masks = torch.from_numpy(np.stack([synth.soft_blob_mask(H, W, 4100 + i) for i in range(n)])).to(DEV)
+        rgb, unary = head.prepare(imgs, masks)
+        out = {}
+        for k, v in enumerate((0, BUILD_ARRAY, BUILD_SMALL_TABLE)):     # SMALL_TABLE: a 1024-bucket first attempt, so every frame takes the overflow path
+            out[k] = crf_soft_batched(rgb, unary, W, H, 0.0, 0.0, 5.0, 60.0, 5.0, iters, want_q=True, want_nvert=True, build=v)
+        same_map = bool(torch.equal(out[0][0], out[1][0])) and bool(torch.equal(out[0][0], out[2][0]))
+        dq = max(float((out[0][1] - out[1][1]).abs().max()), float((out[0][1] - out[2][1]).abs().max()))
+        report(f"crf build variants {H}x{W} x{n} T={iters}: MAP identical {same_map}, max |dQ| {dq:.2e}, vertices {out[0][2][:, 1].tolist()} vs "
+               f"{out[1][2][:, 1].tolist()} vs {out[2][2][:, 1].tolist()} (packed / array-of-keys / packed after a table overflow)")
+        assert same_map and dq == 0.0 and torch.equal(out[0][2], out[1][2]) and torch.equal(out[0][2], out[2][2])
 
 
 @pytest.mark.parametrize("kind,H,W,n", [("smooth", 120, 214, 3), ("noise", 120, 214, 3), ("smooth", 480, 854, 2), ("noise", 480, 854, 2),
@@ -125,7 +126,7 @@ def test_crf_sort_build_identical(kind, H, W, n, report):
     res = {}
     for pots in ((0.0, 0.0, 5.0, 60.0, 5.0), (3.0, 3.0, 5.0, 60.0, 5.0)):
         a = crf_soft_batched(rgb, unary, W, H, *pots, 5, want_q=True, want_nvert=True, build=0)
-        b = crf_soft_batched(rgb, unary, W, H, *pots, 5, want_q=True, want_nvert=True, build=3)
+        b = crf_soft_batched(rgb, unary, W, H, *pots, 5, want_q=True, want_nvert=True, build=BUILD_SORT)
         res[pots[0]] = (bool(torch.equal(a[0], b[0])), float((a[1] - b[1]).abs().max()), bool(torch.equal(a[2], b[2])), a[2][:, 1].tolist())
     report(f"crf sort build vs packed build [{kind} {H}x{W} x{n}]: appearance only: MAP equal {res[0.0][0]}, max |dQ| {res[0.0][1]:.1e}, "
            f"vertex counts equal {res[0.0][2]} {res[0.0][3]}; both potentials: {res[3.0][:3]}")
@@ -285,9 +286,9 @@ def test_crf_blur_pairs_identical(kind, params, iters, report):
     rgb = torch.from_numpy(np.stack([gen(H, W, 4500 + i) for i in range(F)])).to(DEV)
     un = torch.from_numpy(np.stack([_unary(synth.soft_blob_mask(H, W, 4500 + i)) for i in range(F)])).to(DEV)
     out = {}
-    for seq in (0, 4):                                   # build bits: 4 = RCF_CRF_BLUR_SEQUENTIAL >> 8
+    for seq in (0, BLUR_SEQUENTIAL):
         out[seq] = crf_soft_batched(rgb, un, W, H, *params, iters, want_q=True, want_nvert=True, build=seq)
-    same = all(bool(torch.equal(a, b)) for a, b in zip(out[0], out[4]))
+    same = all(bool(torch.equal(a, b)) for a, b in zip(out[0], out[BLUR_SEQUENTIAL]))
     report(f"crf blur pairs vs one launch per axis ({kind}, params {params}, T={iters}): MAP / Q / vertex counts identical: {same}; "
            f"vertices {out[0][2].tolist()}")
     assert same
@@ -310,10 +311,9 @@ def test_crf_tile_splat_identical(kind, size, params, iters, sym, report):
     gen = synth.smooth_rgb if kind == "smooth" else synth.noise_rgb
     rgb = torch.from_numpy(np.stack([gen(H, W, 4700 + i) for i in range(F)])).to(DEV)
     un = torch.from_numpy(np.stack([_unary(synth.soft_blob_mask(H, W, 4700 + i)) for i in range(F)])).to(DEV)
-    GATHER, TILES, SEPARATE, SMALL = 0x4000 >> 8, 0x8000 >> 8, 0x10000 >> 8, 2
     out = {}
-    for name, flags in (("gather", GATHER), ("default", 0), ("tiles", TILES), ("tiles+overflow", TILES | SMALL),
-                        ("tiles, slice and sums apart", TILES | SEPARATE)):
+    for name, flags in (("gather", SPLAT_GATHER), ("default", 0), ("tiles", SPLAT_TILES), ("tiles+overflow", SPLAT_TILES | BUILD_SMALL_TABLE),
+                        ("tiles, slice and sums apart", SPLAT_TILES | SLICE_SPLAT_SEPARATE)):
         out[name] = crf_soft_batched(rgb, un, W, H, *params, iters, want_q=True, want_nvert=True, symmetric=sym, build=flags)
     same = {k: all(bool(torch.equal(a, b)) for a, b in zip(out["gather"], v)) for k, v in out.items() if k != "gather"}
     report(f"crf tile splat vs gather ({kind} {H}x{W}, params {params}, T={iters}, symmetric {sym}): MAP / Q / vertex counts "
@@ -326,7 +326,6 @@ def test_crf_forms_agree_on_random_calls(report):
     the list walk, the tile splat (default rule and forced, fused and separate slice, small-table overflow) and the sort build give the
     same MAP, marginals and vertex counts bit for bit (tools/fuzz_crf.py runs hundreds of these)."""
     rng = np.random.default_rng(5)
-    GATHER, TILES, SEPARATE, SMALL, SORT = 0x4000 >> 8, 0x8000 >> 8, 0x10000 >> 8, 2, 3
     bad = []
     for c in range(40):
         H, W, F, T = int(rng.integers(5, 201)), int(rng.integers(5, 201)), int(rng.integers(1, 5)), int(rng.integers(0, 4))
@@ -339,7 +338,8 @@ def test_crf_forms_agree_on_random_calls(report):
         sym = bool(not two and rng.integers(0, 3) == 0)
         params = (3.0, 3.0, 5.0, 60.0, 5.0) if two else (0.0, 0.0, 5.0, 60.0, 5.0)
         ref = None
-        for name, fl in (("gather", GATHER), ("default", 0), ("tiles", TILES), ("tiles separate", TILES | SEPARATE), ("tiles overflow", TILES | SMALL), ("sort", SORT)):
+        for name, fl in (("gather", SPLAT_GATHER), ("default", 0), ("tiles", SPLAT_TILES), ("tiles separate", SPLAT_TILES | SLICE_SPLAT_SEPARATE),
+                         ("tiles overflow", SPLAT_TILES | BUILD_SMALL_TABLE), ("sort", BUILD_SORT)):
             r = crf_soft_batched(rgb, un, W, H, *params, T, want_q=True, want_nvert=True, symmetric=sym, build=fl)
             if ref is None:
                 ref = r

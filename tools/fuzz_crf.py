@@ -5,11 +5,10 @@ import os, sys, numpy as np, torch
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 import rcf_amd  # noqa
 from rcf_amd import synth
-from rcf_amd.crf import crf_soft_batched
+from rcf_amd.crf import BUILD_SMALL_TABLE, BUILD_SORT, SLICE_SPLAT_SEPARATE, SPLAT_GATHER, SPLAT_TILES, crf_soft_batched
 
 cases = int(sys.argv[1]) if len(sys.argv) > 1 else 60
 rng = np.random.default_rng(int(sys.argv[2]) if len(sys.argv) > 2 else 0)
-GATHER, TILES, SEPARATE, SMALL, SORT = 0x4000 >> 8, 0x8000 >> 8, 0x10000 >> 8, 2, 3
 bad = 0
 for c in range(cases):
     H, W, F = int(rng.integers(5, 261)), int(rng.integers(5, 261)), int(rng.integers(1, 6))
@@ -26,7 +25,8 @@ for c in range(cases):
     sym = bool(not two and rng.integers(0, 3) == 0)
     params = (3.0, 3.0, 5.0, 60.0, 5.0) if two else (0.0, 0.0, float(rng.choice([5.0, 10.0])), float(rng.choice([20.0, 60.0])), float(rng.choice([5.0, 20.0])))
     ref = None
-    for name, fl in (("gather", GATHER), ("default", 0), ("tiles", TILES), ("tiles separate", TILES | SEPARATE), ("tiles overflow", TILES | SMALL), ("sort", SORT)):
+    for name, fl in (("gather", SPLAT_GATHER), ("default", 0), ("tiles", SPLAT_TILES), ("tiles separate", SPLAT_TILES | SLICE_SPLAT_SEPARATE),
+                     ("tiles overflow", SPLAT_TILES | BUILD_SMALL_TABLE), ("sort", BUILD_SORT)):
         r = crf_soft_batched(rgb, un, W, H, *params, T, want_q=True, want_nvert=True, symmetric=sym, build=fl)
         if ref is None:
             ref = r

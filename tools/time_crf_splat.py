@@ -4,9 +4,8 @@ import os, sys, numpy as np, torch
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 import rcf_amd
 from rcf_amd import synth
-from rcf_amd.crf import crf_soft_batched
+from rcf_amd.crf import BUILD_SORT, SLICE_SPLAT_SEPARATE, SPLAT_GATHER, SPLAT_TILES, crf_soft_batched
 n, H, W = 8, 480, 854
-GATHER, TILES, SEPARATE = 0x4000 >> 8, 0x8000 >> 8, 0x10000 >> 8
 
 
 def timed(fn, reps=10):
@@ -19,7 +18,7 @@ def timed(fn, reps=10):
     return e0.elapsed_time(e1) / reps
 
 
-for kind, iters, build in (("smooth", 5, 0), ("smooth", 50, 0), ("smooth", 0, 0), ("noise", 5, 0), ("noise", 5, 3)):
+for kind, iters, build in (("smooth", 5, 0), ("smooth", 50, 0), ("smooth", 0, 0), ("noise", 5, 0), ("noise", 5, BUILD_SORT)):
     make = synth.noise_rgb if kind == "noise" else synth.smooth_rgb
     imgs = torch.from_numpy(np.stack([synth.normalize_rgb(make(H, W, 4000 + i)) for i in range(n)])).cuda()
     masks = torch.from_numpy(np.stack([synth.soft_blob_mask(H, W, 4000 + i) for i in range(n)])).cuda()
@@ -27,7 +26,7 @@ for kind, iters, build in (("smooth", 5, 0), ("smooth", 50, 0), ("smooth", 0, 0)
     rgb, unary = head.prepare(imgs, masks)
     row = []
     for rnd in range(2):
-        for name, fl in (("gather", GATHER), ("default", 0), ("separate", SEPARATE), ("tiles", TILES)):
+        for name, fl in (("gather", SPLAT_GATHER), ("default", 0), ("separate", SLICE_SPLAT_SEPARATE), ("tiles", SPLAT_TILES)):
             t = timed(lambda: crf_soft_batched(rgb, unary, W, H, 0.0, 0.0, head.scomp, head.sxy, head.srgb, iters, build=build | fl)) / n
             row.append(f"{name} {t:.4f}")
     print(f"CRF {kind} T={iters} build {build} x{n} ms/frame | " + " | ".join(row))
