@@ -380,14 +380,23 @@ __global__ void __launch_bounds__(RED_THREADS) colreduce3_kernel(F f, long rows,
     }
 }
 
+// Biased variance from the two column sums.  With ONE value per channel it is exactly 0, and sum x^2 / n - mean^2 must not be
+// asked: StatsOp rounds x^2 to fp32 before the fp64 sum, so the difference is 2^-24 x^2 of noise (4e-6 at |x| = 10 against
+// eps = 1e-5) that would decide invstd in place of eps.  From two values on, that noise stands against a real variance.
+__device__ __forceinline__ double batch_var(double sum, double sumsq, double count) {
+    if (count == 1.0) return 0.0;
+    const double m = sum / count;
+    const double var = sumsq / count - m * m;
+    return var < 0 ? 0 : var;
+}
+
 __global__ void bn_finalize_kernel(const double *__restrict__ sums, double count, int C, float eps, float momentum,
                                    float *__restrict__ mean, float *__restrict__ invstd, float *__restrict__ rmean,
                                    float *__restrict__ rvar) {
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
     if (c >= C) return;
     const double m = sums[c] / count;
-    double var = sums[C + c] / count - m * m;
-    if (var < 0) var = 0;
+    const double var = batch_var(sums[c], sums[C + c], count);
     mean[c] = (float)m;
     invstd[c] = (float)(1.0 / sqrt(var + (double)eps));
     if (rmean) rmean[c] = (1.f - momentum) * rmean[c] + momentum * (float)m;
@@ -459,8 +468,7 @@ __global__ void __launch_bounds__(512) sum_finalize_kernel(const double *__restr
     }
     if (fin.on) {                                          // bn_finalize_kernel's arithmetic
         const double m = t0 / fin.count;
-        double var = t1 / fin.count - m * m;
-        if (var < 0) var = 0;
+        const double var = batch_var(t0, t1, fin.count);
         fin.mean[c] = (float)m;
         fin.invstd[c] = (float)(1.0 / sqrt(var + (double)fin.eps));
         if (fin.rmean) fin.rmean[c] = (1.f - fin.momentum) * fin.rmean[c] + fin.momentum * (float)m;
