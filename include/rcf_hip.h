@@ -458,7 +458,8 @@ int rcf_colsum_mp(const void *x, int xdt, long rows, int C, int pitch, float *ou
                   size_t workspace_bytes, void *stream);
 
 /* ---- pooling / resize / layout ------------------------------------------------------------------
- * MaxPool2d(3,2,1): models/resnet.py:577.  argmax: uint8 window position (r*3+s), first max wins. */
+ * MaxPool2d(3,2,1): models/resnet.py:577.  argmax: uint8 window position (r*3+s), first max wins.  Both directions answer
+ * RCF_EINVAL unless Ho = (H - 1) / 2 + 1 and Wo = (W - 1) / 2 + 1 (y, dy and argmax are indexed by them) and every size is positive. */
 int rcf_maxpool3x3s2_fwd_f32(const float *x, float *y, uint8_t *argmax, int N, int H, int W, int C, int Ho,
                              int Wo, void *stream);
 int rcf_maxpool3x3s2_bwd_f32(const float *dy, const uint8_t *argmax, float *dx, int N, int H, int W, int C,

@@ -643,7 +643,8 @@ extern "C" int rcf_split_rect_f32(const float *src, float *inside, float *outsid
 
 extern "C" int rcf_maxpool3x3s2_fwd_mp(const void *x, void *y, int dt, uint8_t *argmax, int N, int H, int W, int C, int Ho,
                                        int Wo, void *stream) {
-    if (!x || !y || !argmax || C % 4 || Ho != (H + 2 - 3) / 2 + 1 || Wo != (W + 2 - 3) / 2 + 1) return RCF_EINVAL;
+    if (!x || !y || !argmax || N <= 0 || H <= 0 || W <= 0 || C <= 0 || C % 4) return RCF_EINVAL;
+    if (Ho != (H + 2 - 3) / 2 + 1 || Wo != (W + 2 - 3) / 2 + 1) return RCF_EINVAL;
 #define RCF_CALL(T)                                                                                               \
     hipLaunchKernelGGL(maxpool_fwd_kernel<T>, dim3(ew_blocks((long)N * Ho * Wo * (C / 4))), dim3(256), 0,        \
                        rcf_stream(stream), (const T *)x, (T *)y, argmax, N, H, W, C, Ho, Wo)
@@ -659,7 +660,8 @@ extern "C" int rcf_maxpool3x3s2_fwd_f32(const float *x, float *y, uint8_t *argma
 
 extern "C" int rcf_maxpool3x3s2_bwd_mp(const void *dy, const uint8_t *argmax, void *dx, int dt, int N, int H, int W, int C,
                                        int Ho, int Wo, void *stream) {
-    if (!dy || !dx || !argmax || C % 4) return RCF_EINVAL;
+    if (!dy || !dx || !argmax || N <= 0 || H <= 0 || W <= 0 || C <= 0 || C % 4) return RCF_EINVAL;
+    if (Ho != (H + 2 - 3) / 2 + 1 || Wo != (W + 2 - 3) / 2 + 1) return RCF_EINVAL;       // argmax and dy are read by them
 #define RCF_CALL(T)                                                                                                       \
     hipLaunchKernelGGL(maxpool_bwd_kernel<T>, dim3(ew_blocks((long)N * H * W * (C / 4))), dim3(256), 0, rcf_stream(stream), \
                        (const T *)dy, argmax, (T *)dx, N, H, W, C, Ho, Wo)
