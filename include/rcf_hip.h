@@ -106,6 +106,12 @@ typedef struct {
 #define RCF_CONV_NO_WGRAD_XCD 0x20u
 #define RCF_CONV_NO_COLMAP 0x40u
 #define RCF_CONV_KORDER_NATURAL 0x80u
+/*   NO_TAP_SKIP              the forward / data-gradient tile kernel walks every K-step and a frame region's pixels row-major
+ *                            strip by strip (default, on frame regions and with a source frame: a tile drops the K-steps of
+ *                            taps that none of its rows can read -- outside the image, or off a data gradient's source frame --
+ *                            and the frame is walked by depth so that whole tiles share such taps; csrc/region_order.h).  The
+ *                            dropped terms are exact zeros: bit-identical. */
+#define RCF_CONV_NO_TAP_SKIP 0x400u
 /* 1x1 convs with 4 / 8 / 16 output channels on 64 .. 512 input channels (the decode heads' classifiers) run as streaming fp32
  * passes (csrc/thin.hip) instead of GEMM tiles with a handful of live columns; this bit keeps them on the GEMM kernels (A/B, tests) */
 #define RCF_CONV_NO_THIN 0x100u
@@ -199,6 +205,12 @@ int rcf_conv2d_dgrad_f32(const float *dy, const float *w, float *dx, const rcf_c
 int rcf_conv2d_dgrad_region_f32(const float *dy, const float *w, float *dx, const rcf_conv_shape *s,
                                 const rcf_conv_region *region, int beta, void *workspace, size_t workspace_bytes,
                                 void *stream);
+/* The same with a source frame: dy_band > 0 takes dy as ZERO off the border frame of that thickness of its [Ho, Wo] grid and does
+ * not read it there (the contract of the resize kernels' `frame`): the caller passes the whole gradient instead of a copy with a
+ * zeroed interior, and tiles whose taps all fall off the frame skip them.  Stride 1, at most 32 taps, no DY_PLANES. */
+int rcf_conv2d_dgrad_region_band_f32(const float *dy, const float *w, float *dx, const rcf_conv_shape *s,
+                                     const rcf_conv_region *region, int dy_band, int beta, void *workspace,
+                                     size_t workspace_bytes, void *stream);
 /* The data gradient of a conv whose INPUT is the output of a training-mode batch norm + ReLU (the bottlenecks' bn1 -> conv2,
  * bn2 -> conv3, bn3 + identity -> the next block's conv1; models/resnet.py:268-302), and, from the same kernel's epilogue, the
  * two sums that norm's backward needs: sums2[2*Cin] = [sum g | sum g * xhat] with g = dx masked by the norm's ReLU sign bits

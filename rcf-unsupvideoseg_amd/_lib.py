@@ -41,6 +41,7 @@ WARP_PER_PIXEL = 0x100
 BN_SWEEP_OFF, BN_SWEEP_ALWAYS, BN_Y_PLANES_ONLY, BN_DX_PLANES = 0x1, 0x2, 0x4, 0x8
 CONV_H2P_NEVER, CONV_H2P_ALWAYS = 0x8, 0x10
 CONV_NO_WGRAD_XCD, CONV_NO_COLMAP, CONV_KORDER_NATURAL, CONV_NO_THIN, CONV_NT_STORES = 0x20, 0x40, 0x80, 0x100, 0x200
+CONV_NO_TAP_SKIP = 0x400        # every K-step, frames row-major strip by strip (RCF_CONV_NO_TAP_SKIP)
 
 
 def CONV_FP32_MFMA(v):
@@ -99,6 +100,7 @@ PROTOS = {
     "rcf_conv2d_fwd_f32": (c_int, [P, P, P, P, _CS, c_int, c_float, c_int, P]),
     "rcf_conv2d_fwd_region_f32": (c_int, [P, P, P, P, _CS, _CR, c_int, c_float, c_int, P]),
     "rcf_conv2d_dgrad_region_f32": (c_int, [P, P, P, _CS, _CR, c_int, P, c_size_t, P]),
+    "rcf_conv2d_dgrad_region_band_f32": (c_int, [P, P, P, _CS, _CR, c_int, c_int, P, c_size_t, P]),
     "rcf_conv2d_wgrad_region_workspace_bytes": (c_size_t, [_CS, _CR]),
     "rcf_conv2d_wgrad_region_f32": (c_int, [P, P, P, _CS, _CR, c_int, P, c_size_t, P]),
     "rcf_gemm_nt_f32": (c_int, [P, c_int, P, c_int, P, P, c_int, c_int, c_int, c_int, c_int, c_float, c_int, P, P, P, P,

@@ -65,6 +65,10 @@ struct IgemmParams {
     int ry0, rx0, rh, rw;
     int rband;                    // > 0: only the frame of this thickness along the rectangle's border
     int rr;                       // rows per image: rh*rw, or the frame's pixel count
+    int rorder;                   // forward / data-gradient kernels: order of a frame's pixels (region_order.h RCF_REGION_*)
+    // igemm_conv_x3_kernel: walk only the K-steps whose tap some row of the tile can read (0: every step, the plain loop)
+    int tapskip;
+    int src_band;                 // > 0: the source is taken as zero off its border frame of this thickness (and not read there)
     // batched GEMM (rcf_gemm_nt_batched_f32): blockIdx.y = i0 * batch1 + i1 selects the operands of one product
     int batch1;
     long a_bs0, a_bs1, b_bs0, b_bs1, y_bs0, y_bs1;     // element strides of A / B / Y over the two batch indices
@@ -97,31 +101,10 @@ struct IgemmParams {
     int add_pitch;
 };
 
-// pixel `pix` (0 <= pix < rr) of a region -> image coordinates.  Rectangle: row-major.  Frame of thickness t: the top
-// strip (t x rw), the bottom strip, then the left and right strips (each (rh - 2t) x t), all row-major.
+// pixel `pix` of a region in the row-major order (region_order.h): the weight gradients (the order of their sums over pixels) and
+// the kernels without tap lists (conv_h2d_kernel, conv_h2p_kernel)
 __device__ __forceinline__ void region_yx(int pix, int ry0, int rx0, int rh, int rw, int t, int &y, int &x) {
-    if (t <= 0) {
-        const int yr = pix / rw;
-        y = yr + ry0;
-        x = pix - yr * rw + rx0;
-        return;
-    }
-    const int strip = t * rw;
-    if (pix < 2 * strip) {
-        const int bottom = pix >= strip;
-        const int q = pix - (bottom ? strip : 0);
-        const int yr = q / rw;
-        y = ry0 + yr + (bottom ? rh - t : 0);
-        x = rx0 + q - yr * rw;
-    } else {
-        int q = pix - 2 * strip;
-        const int side = t * (rh - 2 * t);
-        const int right = q >= side;
-        q -= right ? side : 0;
-        const int yr = q / t;
-        y = ry0 + t + yr;
-        x = rx0 + q - yr * t + (right ? rw - t : 0);
-    }
+    rcf_region_yx(pix, ry0, rx0, rh, rw, t, RCF_REGION_ROWMAJOR, y, x);
 }
 
 __device__ __forceinline__ int fast_div(int k, unsigned magic) { return magic ? (int)__umulhi((unsigned)k, magic) : k; }
@@ -580,7 +563,7 @@ __device__ __forceinline__ void conv_epilogue_tr(const IgemmParams &p, f32x16 (&
         if (rowok[mr] && !full) {
             const int n = row / HoWo;
             int y, x;
-            region_yx(row - n * HoWo, p.ry0, p.rx0, p.rh, p.rw, p.rband, y, x);
+            rcf_region_yx(row - n * HoWo, p.ry0, p.rx0, p.rh, p.rw, p.rband, p.rorder, y, x);
             lin[mr] = ((long)n * p.Ho + y) * p.Wo + x;
         }
     }
@@ -785,12 +768,17 @@ __device__ __forceinline__ void conv_epilogue_tr(const IgemmParams &p, f32x16 (&
 // PRE (NP == 2 only): the weight operand arrives split (p.b_pairs: two fp16 planes)
 // TR: transposed accumulator tiles (mma_x3 SWAP) and the 16-byte epilogue; every instance is launched with TR = true
 // (the batch-norm statistics, column sums, are a butterfly over the pixels = lanes of a half-wavefront there)
-template <int MR, int NR, int WM, int WN, bool STRIDED, bool DGRAD = false, int NP = 3, bool PRE = false, bool TR = DGRAD, bool BST = false>
+// LIST: the K loop walks a per-tile list of taps (below) instead of every K-step -- its own instantiation, launched for p.tapskip:
+// the 128 x 256 tile runs at 252 of 256 registers, and a second loop beside the plain one in the same kernel spilled both
+template <int MR, int NR, int WM, int WN, bool STRIDED, bool DGRAD = false, int NP = 3, bool PRE = false, bool TR = DGRAD, bool BST = false,
+          bool LIST = false>
 __global__ void __launch_bounds__(64 * WM * WN, (MR * NR >= 8 && WM * WN == 4) ? 2 : 1) igemm_conv_x3_kernel(IgemmParams p) {
+    static_assert(!(LIST && STRIDED), "the tap list is for unit-stride launches");
     constexpr int NT = 64 * WM * WN;
     constexpr int BM = 32 * MR * WM, BN = 32 * NR * WN, BKT = 16;
     constexpr int PA = BM * 32, PB = BN * 32, STAGE = NP * (PA + PB);
     __shared__ __attribute__((aligned(16))) char smem[2 * STAGE];
+    __shared__ unsigned tapsh[LIST ? WM * WN : 1];            // per wave: the taps its rows can read (the tap-list loop)
 
     // XCD aware: block id % 8 is the XCD; its blocks b, b + 8, .. walk the column tiles of one row tile, then the next row tile
     // of the XCD's own contiguous range (the rows a dilated tap reaches belong to neighbouring row tiles: same L2;
@@ -841,7 +829,7 @@ __global__ void __launch_bounds__(64 * WM * WN, (MR * NR >= 8 && WM * WN == 4) ?
         } else if (m < p.M) {
             const int n = m / HoWo;
             int y, x;
-            region_yx(m - n * HoWo, p.ry0, p.rx0, p.rh, p.rw, p.rband, y, x);
+            rcf_region_yx(m - n * HoWo, p.ry0, p.rx0, p.rh, p.rw, p.rband, p.rorder, y, x);
             ay[i] = y * p.up + p.off;
             ax[i] = x * p.up + p.off;
             abase[i] = (n - n_first) * (int)p.a_img_stride + (STRIDED ? 0 : (ay[i] * p.Ws + ax[i]) * p.a_pitch);
@@ -863,7 +851,10 @@ __global__ void __launch_bounds__(64 * WM * WN, (MR * NR >= 8 && WM * WN == 4) ?
     // of the step); B (weights, L2 resident) one step ahead.
     f32x4 ra[2][A_PASS], rb[B_PASS];
 
-    auto load_a = [&](int kt, f32x4 (&dst)[A_PASS]) {
+    // BAND (the tap-list loop only): a source off the frame p.src_band is zero by contract and not read
+    const int band_lo = p.src_band > 0 ? p.src_band : (1 << 30);
+    auto load_a = [&](int kt, f32x4 (&dst)[A_PASS], auto BAND_) {
+        constexpr bool BAND = decltype(BAND_)::value;
         const int k = kt * BKT + kq * 4;
         const bool kv = k < p.K;
         // position k of the K loop = (channel chunk q, tap rs, channel inside the chunk); natural order: ONE chunk of Cs
@@ -887,6 +878,8 @@ __global__ void __launch_bounds__(64 * WM * WN, (MR * NR >= 8 && WM * WN == 4) ?
                 off = abase[i] + (ty * p.Ws + tx) * p.a_pitch + c;
             } else {
                 v = (int)kv & (int)((unsigned)ty < (unsigned)p.Hs) & (int)((unsigned)tx < (unsigned)p.Ws);
+                if constexpr (BAND)
+                    v &= (int)(ty < band_lo) | (int)(ty >= p.Hs - band_lo) | (int)(tx < band_lo) | (int)(tx >= p.Ws - band_lo);
                 off = abase[i] + tapoff;
             }
             // invalid -> offset with bit 31 set (beyond num_records): the load returns zeros without touching memory
@@ -963,46 +956,123 @@ __global__ void __launch_bounds__(64 * WM * WN, (MR * NR >= 8 && WM * WN == 4) ?
 
     const int arow0 = wm * 32 * MR, brow0 = wn * 32 * NR;
     const int KT = (p.K + BKT - 1) / BKT;
-    load_a(0, ra[0]);
-    load_b(0);
-    load_a(1, ra[1]);                        // past the end of K: out-of-range offsets, zeros
-    store_tile(0, ra[0]);
-    __syncthreads();
-    // K-step kt: MFMAs on stage kt&1 while B(kt+1) and A(kt+2) are in flight; then A(kt+1) (loaded a step ago) and
-    // B(kt+1) are split into stage (kt+1)&1.  B is issued before A so that its wait does not cover the new A loads.
-    int kt = 0;
-    for (; kt + 2 <= KT - 1; kt += 2) {
-        {   // even step: next A tile is ra[1], the set freed by this step's LDS store is ra[0]
+    // Tap list (p.tapskip, set by the launch for multi-tap, unit-stride, unbatched shapes whose K-steps lie inside one tap): bit rs
+    // of `taps` = some row of this tile has a source pixel at tap rs that can be non-zero (region_order.h rcf_row_taps).  In a
+    // frame region whole tiles share the taps that leave the image; their K-steps would load zeros and multiply them.  The loop
+    // below walks the remaining steps in their original order -- the same sums, minus terms that are exactly zero.
+    if constexpr (LIST) {
+        {
+            const int RS = p.K / p.Cs;
+            unsigned mine = 0u;
+#pragma unroll
+            for (int i = 0; i < A_PASS; ++i) mine |= rcf_row_taps(ay[i], ax[i], RS / p.S, p.S, p.step, p.Hs, p.Ws, p.src_band);
+            unsigned taps = 0u;
+            for (int rs = 0; rs < RS; ++rs) taps |= (unsigned)(__ballot((mine >> rs) & 1u) != 0ull) << rs;
+            tapsh[wave] = taps;
+            __syncthreads();
+            taps = 0u;
+#pragma unroll
+            for (int w = 0; w < WM * WN; ++w) taps |= tapsh[w];
+            taps = (p.tapskip & 2) ? ~0u : (unsigned)__builtin_amdgcn_readfirstlane((int)taps);   // 2: the list holds every tap
+            // first listed K-step after kt (KT: none left -- a step past the end of K loads zeros, like the plain loop's look-ahead)
+            auto next = [&](int kt) {
+                while (++kt < KT) {
+                    const int k = kt * BKT;
+                    const int rem = k - fast_div(k, p.rsch_magic) * p.rsch;
+                    if ((taps >> fast_div(rem, p.kch_magic)) & 1u) return kt;
+                }
+                return KT;
+            };
+            // the listed steps number n: every tap owns KT / RS whole steps (the launch's condition for a list that drops any)
+            int n = (p.tapskip & 2) ? KT : __builtin_popcount(taps & (RS >= 32 ? ~0u : (1u << RS) - 1u)) * (KT / RS);
+            n = n < 1 ? 1 : n;                   // nothing to read: one step past the end of K (zeros)
+            // the plain loop below with the step numbers it, it + 1, .. replaced by the list's: s1 / s2 = the steps one / two ahead
+            int s1 = next(-1), s2;
+            load_a(s1, ra[0], std::true_type{});
+            load_b(s1);
+            s1 = next(s1);
+            load_a(s1, ra[1], std::true_type{});
+            store_tile(0, ra[0]);
+            __syncthreads();
+            s2 = next(s1);
+            int it = 0;
+            for (; it + 2 <= n - 1; it += 2) {
+                {
+                    load_b(s1);
+                    load_a(s2, ra[0], std::true_type{});
+                    __builtin_amdgcn_sched_barrier(0);
+                    const char *As = smem;
+                    mma_x3<MR, NR, PA, PB, false, NP, TR>(As, As + NP * PA, arow0, brow0, lane, acc);
+                    store_tile(1, ra[1]);
+                    __syncthreads();
+                }
+                s1 = next(s2);
+                {
+                    load_b(s2);
+                    load_a(s1, ra[1], std::true_type{});
+                    __builtin_amdgcn_sched_barrier(0);
+                    const char *As = smem + STAGE;
+                    mma_x3<MR, NR, PA, PB, false, NP, TR>(As, As + NP * PA, arow0, brow0, lane, acc);
+                    store_tile(0, ra[0]);
+                    __syncthreads();
+                }
+                s2 = next(s1);
+            }
+            if (it < n - 1) {
+                load_b(s1);
+                __builtin_amdgcn_sched_barrier(0);
+                const char *As = smem;
+                mma_x3<MR, NR, PA, PB, false, NP, TR>(As, As + NP * PA, arow0, brow0, lane, acc);
+                store_tile(1, ra[1]);
+                __syncthreads();
+                ++it;
+            }
+            const char *As = smem + (it & 1) * STAGE;
+            mma_x3<MR, NR, PA, PB, false, NP, TR>(As, As + NP * PA, arow0, brow0, lane, acc);
+        }
+    } else {
+        load_a(0, ra[0], std::false_type{});
+        load_b(0);
+        load_a(1, ra[1], std::false_type{});                        // past the end of K: out-of-range offsets, zeros
+        store_tile(0, ra[0]);
+        __syncthreads();
+        // K-step kt: MFMAs on stage kt&1 while B(kt+1) and A(kt+2) are in flight; then A(kt+1) (loaded a step ago) and
+        // B(kt+1) are split into stage (kt+1)&1.  B is issued before A so that its wait does not cover the new A loads.
+        int kt = 0;
+        for (; kt + 2 <= KT - 1; kt += 2) {
+            {   // even step: next A tile is ra[1], the set freed by this step's LDS store is ra[0]
+                load_b(kt + 1);
+                load_a(kt + 2, ra[0], std::false_type{});
+                __builtin_amdgcn_sched_barrier(0);
+                const char *As = smem;
+                mma_x3<MR, NR, PA, PB, false, NP, TR>(As, As + NP * PA, arow0, brow0, lane, acc);
+                store_tile(1, ra[1]);
+                __syncthreads();
+            }
+            {   // odd step
+                load_b(kt + 2);
+                load_a(kt + 3, ra[1], std::false_type{});
+                __builtin_amdgcn_sched_barrier(0);
+                const char *As = smem + STAGE;
+                mma_x3<MR, NR, PA, PB, false, NP, TR>(As, As + NP * PA, arow0, brow0, lane, acc);
+                store_tile(0, ra[0]);
+                __syncthreads();
+            }
+        }
+        if (kt < KT - 1) {                       // one more full step (stage 0 -> stage 1)
             load_b(kt + 1);
-            load_a(kt + 2, ra[0]);
             __builtin_amdgcn_sched_barrier(0);
             const char *As = smem;
             mma_x3<MR, NR, PA, PB, false, NP, TR>(As, As + NP * PA, arow0, brow0, lane, acc);
             store_tile(1, ra[1]);
             __syncthreads();
+            ++kt;
         }
-        {   // odd step
-            load_b(kt + 2);
-            load_a(kt + 3, ra[1]);
-            __builtin_amdgcn_sched_barrier(0);
-            const char *As = smem + STAGE;
+        {
+            const char *As = smem + (kt & 1) * STAGE;
             mma_x3<MR, NR, PA, PB, false, NP, TR>(As, As + NP * PA, arow0, brow0, lane, acc);
-            store_tile(0, ra[0]);
-            __syncthreads();
         }
-    }
-    if (kt < KT - 1) {                       // one more full step (stage 0 -> stage 1)
-        load_b(kt + 1);
-        __builtin_amdgcn_sched_barrier(0);
-        const char *As = smem;
-        mma_x3<MR, NR, PA, PB, false, NP, TR>(As, As + NP * PA, arow0, brow0, lane, acc);
-        store_tile(1, ra[1]);
-        __syncthreads();
-        ++kt;
-    }
-    {
-        const char *As = smem + (kt & 1) * STAGE;
-        mma_x3<MR, NR, PA, PB, false, NP, TR>(As, As + NP * PA, arow0, brow0, lane, acc);
+
     }
 
     conv_epilogue_tr<MR, NR, WM, WN, DGRAD, NP, BST>(p, acc, smem, tile_m, m0, n0, ka, kb);
@@ -2055,6 +2125,17 @@ void launch_x3_cfg_np(IgemmParams &p, bool strided, hipStream_t st, int batches)
     p.colmap = batches == 1 && p.Ncol % BN == 0 &&
                rcf_colmap_pays(!(p.flags & RCF_CONV_NO_COLMAP), (long)p.M * p.Cs * 4, (long)p.K * p.Ncol * 4, p.mtiles, p.ntiles);
     const dim3 grid((unsigned)(rcf_cdiv(p.mtiles, 8) * 8 * p.ntiles), (unsigned)batches);
+    if (p.tapskip) {                             // the tap-list instances (launch_igemm_x3: never strided or batched)
+        if constexpr (NP == 2 && PRE) {
+            if (p.stats && p.step < 0) {
+                hipLaunchKernelGGL((igemm_conv_x3_kernel<MR, NR, WM, WN, false, true, NP, PRE, true, true, true>), grid, dim3(64 * WM * WN), 0, st, p);
+                return;
+            }
+        }
+        if (p.step < 0) hipLaunchKernelGGL((igemm_conv_x3_kernel<MR, NR, WM, WN, false, true, NP, PRE, true, false, true>), grid, dim3(64 * WM * WN), 0, st, p);
+        else hipLaunchKernelGGL((igemm_conv_x3_kernel<MR, NR, WM, WN, false, false, NP, PRE, true, false, true>), grid, dim3(64 * WM * WN), 0, st, p);
+        return;
+    }
     if constexpr (NP == 2 && PRE) {              // data gradient + the batch-norm backward sums (rcf_conv2d_dgrad_bnsums_f32)
         if (p.stats && p.step < 0) {
             if (strided) hipLaunchKernelGGL((igemm_conv_x3_kernel<MR, NR, WM, WN, true, true, NP, PRE, true, true>), grid, dim3(64 * WM * WN), 0, st, p);
@@ -2185,7 +2266,9 @@ int launch_igemm_x3(IgemmParams &p, hipStream_t st, int batches = 1, int *kernel
     }
     p.s_magic = magic_of(p.S);
     if ((long)p.K * p.Cs >= (1L << 32)) return RCF_EINVAL;
-    if (p.a_split) return launch_h2d(p, st, batches, kernel_only);
+    const bool tap_skip = !(p.flags & RCF_CONV_NO_TAP_SKIP);
+    p.rorder = RCF_REGION_ROWMAJOR;             // conv_h2d_kernel / conv_h2p_kernel: no tap lists, the order they always had
+    if (p.a_split) return p.src_band > 0 ? RCF_EINVAL : launch_h2d(p, st, batches, kernel_only);
     if (kernel_only) {
         *kernel_only = h2p_eligible(p, batches) ? 2 : 1;
         return 0;
@@ -2201,6 +2284,20 @@ int launch_igemm_x3(IgemmParams &p, hipStream_t st, int batches = 1, int *kernel
         p.b_bytes = (int)bytes;
     }
     const bool strided = p.div > 1;
+    {
+        // the tap-list K loop of igemm_conv_x3_kernel: several taps (at most 32: one mask word), whole K-steps inside one tap, unit
+        // stride, one product.  A source frame needs that loop's loads even where the list holds every tap (bit 1).
+        // Frames only: on a whole tensor the edge lines are 3 % of the steps, and the list's step arithmetic cost the 3x3 forward
+        // launches of the step 3 - 8 % (profiles/tap_skip_kernel_stats.txt) -- those keep the plain loop.
+        const int taps = p.K / p.Cs;
+        const bool can = !strided && batches == 1 && p.batch1 == 0 && taps > 1 && taps <= 32 && p.kch % 16 == 0 &&
+                         (p.rband > 0 || p.src_band > 0);
+        if (p.src_band > 0 && (strided || batches != 1 || p.batch1 != 0 || taps > 32)) return RCF_EINVAL;
+        p.tapskip = (can && tap_skip) ? 1 : (p.src_band > 0 ? 3 : 0);
+        // ... and frames by depth (region_order.h), so that the rows of a tile share the taps that read nothing; fused
+        // statistics are sums over a tile's pixels and keep the order they were checked under
+        if (p.tapskip == 1 && !p.stats) p.rorder = RCF_REGION_BYDEPTH;
+    }
     if (p.Ncol <= 64 && (long)rcf_cdiv(p.M, 128) * batches < 512) launch_x3_cfg<1, 1, 2, 2>(p, strided, st, batches);   // few rows: 64x64 tiles fill more CUs
     else if (p.Ncol <= 64) launch_x3_cfg<2, 1, 2, 2>(p, strided, st, batches);
     else if (p.Ncol > 128) launch_x3_cfg<2, 4, 2, 2>(p, strided, st, batches);
@@ -2329,7 +2426,7 @@ namespace {
 int conv2d_dgrad_impl(const float *dy, const float *w, float *dx, const rcf_conv_shape *s, const rcf_conv_region *region, int beta,
                       void *workspace, size_t workspace_bytes, void *stream, int *kernel_only, const rcf_bn_bwd_in *bn = nullptr,
                       double *stats = nullptr, int *mtiles_out = nullptr, const float *add = nullptr, int add_pitch = 0,
-                      const unsigned char *add_mask = nullptr);
+                      const unsigned char *add_mask = nullptr, int dy_band = 0);
 // forward launch; kernel_only: report the kernel the call would take instead (rcf_conv_kernel_of)
 int conv2d_fwd_impl(const float *x, const float *w, const float *bias, float *y, const rcf_conv_shape *s,
                     const rcf_conv_region *region, int act, float slope, int beta, double *stats, void *stream, int *kernel_only,
@@ -2519,10 +2616,18 @@ extern "C" int rcf_conv2d_dgrad_f32(const float *dy, const float *w, float *dx, 
 extern "C" int rcf_conv2d_dgrad_region_f32(const float *dy, const float *w, float *dx, const rcf_conv_shape *s,
                                            const rcf_conv_region *region, int beta, void *workspace,
                                            size_t workspace_bytes, void *stream) {
+    return rcf_conv2d_dgrad_region_band_f32(dy, w, dx, s, region, 0, beta, workspace, workspace_bytes, stream);
+}
+
+extern "C" int rcf_conv2d_dgrad_region_band_f32(const float *dy, const float *w, float *dx, const rcf_conv_shape *s,
+                                                const rcf_conv_region *region, int dy_band, int beta, void *workspace,
+                                                size_t workspace_bytes, void *stream) {
     if (int e = check_shape(s)) return e;
     if (!dy || !w || !dx || !rcf_aligned16(dy) || !rcf_aligned16(w) || !rcf_aligned16(dx)) return RCF_EINVAL;
-    if (!region && thin_path(s)) return rcf_thin_dgrad(dy, w, dx, s, beta, rcf_stream(stream));
-    return conv2d_dgrad_impl(dy, w, dx, s, region, beta, workspace, workspace_bytes, stream, nullptr);
+    if (dy_band < 0 || (dy_band > 0 && (!use_x3(s->flags) || s->stride != 1 || 2 * dy_band >= s->Ho || 2 * dy_band >= s->Wo))) return RCF_EINVAL;
+    if (!region && !dy_band && thin_path(s)) return rcf_thin_dgrad(dy, w, dx, s, beta, rcf_stream(stream));
+    return conv2d_dgrad_impl(dy, w, dx, s, region, beta, workspace, workspace_bytes, stream, nullptr, nullptr, nullptr, nullptr, nullptr, 0,
+                             nullptr, dy_band);
 }
 
 extern "C" size_t rcf_conv2d_dgrad_bnsums_workspace_bytes(const rcf_conv_shape *s) {
@@ -2563,10 +2668,14 @@ extern "C" int rcf_conv2d_dgrad_add_f32(const float *dy, const float *w, float *
 namespace {
 int conv2d_dgrad_impl(const float *dy, const float *w, float *dx, const rcf_conv_shape *s, const rcf_conv_region *region, int beta,
                       void *workspace, size_t workspace_bytes, void *stream, int *kernel_only, const rcf_bn_bwd_in *bn, double *stats,
-                      int *mtiles_out, const float *add, int add_pitch, const unsigned char *add_mask) {
+                      int *mtiles_out, const float *add, int add_pitch, const unsigned char *add_mask, int dy_band) {
     if (s->Cout % 4) return RCF_EINVAL;
     IgemmParams p{};
     p.flags = s->flags;
+    if (dy_band > 0) {                           // the source frame lives in igemm_conv_x3_kernel's tap-list loop
+        p.flags |= RCF_CONV_H2P_NEVER;
+        p.src_band = dy_band;
+    }
     if (add) {
         // the masked addend lives in the lean epilogue of the fp16-pair kernels, like the batch-norm sums below
         if (!dgrad_lean_ok(s) || region || beta || !add_mask || add_pitch % 4 || add_pitch < s->Cin || !rcf_aligned16(add))

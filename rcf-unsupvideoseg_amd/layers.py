@@ -971,15 +971,17 @@ def commuted_concat_conv(a, b, conv, tape):
 
     wpt = {}                                     # transposed fp16-pair planes of the two weight halves, made once per backward
 
-    def cdgrad(dy, wt, xshape, dil, out, beta, rdy, region=None):
+    def cdgrad(dy, wt, xshape, dil, out, beta, rdy, region=None, dy_band=0):
         if bf:
+            assert not dy_band
             return ops.conv2d_dgrad_bf16(dy, wt, xshape, 1, dil, dil, out=out, beta=beta, region=region)
         pt = None
         if h2 and rdy is not None:
             pt = wpt.get(id(wt))
             if pt is None:
                 pt = wpt[id(wt)] = ops.weight_pairs_t(wt, rw)
-        return ops.conv2d_dgrad(dy, wt, xshape, 1, dil, dil, out=out, beta=beta, region=region, amax=(rdy, rw), w_pairs_t=pt)
+        return ops.conv2d_dgrad(dy, wt, xshape, 1, dil, dil, out=out, beta=beta, region=region, amax=(rdy, rw), w_pairs_t=pt,
+                                dy_band=dy_band)
 
     Z = cfwd(b.t, wbt, pb, d // 2, rb)
     y = ops.resize_nhwc_fwd(Z, (h, w), False)                              # interior: conv_d(up2(b)) = up2(conv_{d/2}(b))
@@ -990,7 +992,8 @@ def commuted_concat_conv(a, b, conv, tape):
     def bwd():
         rdy = ya.take_grad_range() if h2 else None                         # from the batch norm's backward when it left one
         dy = ya.take_grad()
-        dy_int, dy_band = ops.split_rect(dy, interior)
+        # the band's data gradient reads dy itself with the frame as its contract (fp32 kernels); the 16-bit one a zeroed copy
+        dy_int, dy_band = ops.split_rect(dy, interior, want_outside=bf)
         g4 = ops.resize_nhwc_bwd(dy_int, (hb, wb), False)                  # adjoint of the interior's up-sampling
         rg4 = None
         if h2:
@@ -1010,7 +1013,10 @@ def commuted_concat_conv(a, b, conv, tape):
         if b.needs_grad:
             gb, beta = b.grad_slot()
             dUup = torch.empty_like(Uup)                                   # written (and read) on the bi-frame only
-            cdgrad(dy_band, wbt, Uup.shape, d, dUup, 0, rdy, region=(0, 0, h, w, bi))
+            if bf:
+                cdgrad(dy_band, wbt, Uup.shape, d, dUup, 0, rdy, region=(0, 0, h, w, bi))
+            else:
+                cdgrad(dy, wbt, Uup.shape, d, dUup, 0, rdy, region=(0, 0, h, w, bi), dy_band=bw)
             # the whole-tensor term first, so that the frame term always accumulates (its kernel then only walks the
             # input pixels that can see the frame)
             cdgrad(g4, wbt, b.t.shape, d // 2, gb, beta, rg4)

@@ -440,8 +440,9 @@ def conv2d_fwd_stats(x, w, stride=1, pad=0, dil=1, amax=None, w_pairs=None, bn=N
 
 
 def conv2d_dgrad(dy, w, xshape, stride=1, pad=0, dil=1, out=None, beta=0, region=None, amax=None, w_pairs_t=None,
-                 dy_planes=False, amax_y=None, bn_bwd=None, addend=None):
+                 dy_planes=False, amax_y=None, bn_bwd=None, addend=None, dy_band=0):
     """region = (y0, x0, h, w) in INPUT coordinates: only those pixels of dx are written.  amax = (amax_dy, amax_w);
+    dy_band > 0: dy counts as zero off its border frame of that thickness and is not read there (rcf_conv2d_dgrad_region_band_f32).
     w_pairs_t = weight_pairs_t(w, amax_w), prepared once per weight update.  dy_planes: `dy` holds fp16 pair planes
     (RCF_CONV_DY_PLANES: bn_bwd_apply's dx); amax_y: new_amax() slot for the range of dx (after the accumulation).
     bn_bwd = (x_bn, relu_mask, mean, invstd) of the batch norm + ReLU whose OUTPUT is this conv's input, given when this call is the
@@ -457,10 +458,10 @@ def conv2d_dgrad(dy, w, xshape, stride=1, pad=0, dil=1, out=None, beta=0, region
                     amax=None if amax is None else (None, amax[1], amax[0]), w_pairs2_t=w_pairs_t,
                     flags=_lib.CONV_DY_PLANES if dy_planes else 0, amax_y=amax_y, nt_cols=xshape[3])
     assert tuple(dy.shape) == (s.N, s.Ho, s.Wo, s.Cout)
-    fuse = (bn_bwd is not None and region is None and out.is_contiguous() and bn_bwd[0].dtype == torch.float32 and
+    fuse = (bn_bwd is not None and region is None and not dy_band and out.is_contiguous() and bn_bwd[0].dtype == torch.float32 and
             tuple(bn_bwd[0].shape) == tuple(out.shape) and _lib.load().rcf_conv2d_dgrad_bnsums_ok(byref(s)) == 1)
     if addend is not None:
-        assert beta == 0 and region is None and tuple(addend[0].shape) == tuple(out.shape) and addend[0].dtype == torch.float32
+        assert beta == 0 and region is None and not dy_band and tuple(addend[0].shape) == tuple(out.shape) and addend[0].dtype == torch.float32
         if _lib.load().rcf_conv2d_dgrad_bnsums_ok(byref(s)) != 1:
             raise _lib.RcfHipError("this data gradient cannot take a masked addend (ask ops.dgrad_takes_addend first)")
     need = 0 if w_pairs_t is not None else _lib.load().rcf_conv2d_dgrad_workspace_bytes(byref(s))
@@ -478,6 +479,9 @@ def conv2d_dgrad(dy, w, xshape, stride=1, pad=0, dil=1, out=None, beta=0, region
         ad, am = addend if addend is not None else (None, None)
         call("rcf_conv2d_dgrad_add_f32", _p(dy), _p(weight_rsck(w)), _p(out), byref(s), beta, _p(ad), pitch_of(ad) if ad is not None else 0,
              _p(am), bn, _p(sums2), _p(ws) if fuse else None, need if fuse else 0, _stream())
+    elif dy_band:
+        call("rcf_conv2d_dgrad_region_band_f32", _p(dy), _p(weight_rsck(w)), _p(out), byref(s), _region(region), int(dy_band), beta,
+             _p(ws), need, _stream())
     else:
         call("rcf_conv2d_dgrad_region_f32", _p(dy), _p(weight_rsck(w)), _p(out), byref(s), _region(region), beta, _p(ws),
              need, _stream())

@@ -1,7 +1,7 @@
 """A/B of the training step's schedule and operand format in ONE process (boxes differ by more than the effects): the weight
 gradients on the main stream / on a second stream beside the layer's data gradient / started after it (layers.SCHED.late_wgrad), with
 the fp16 pair planes (layers.SCHED.planes) on and off.  Interleaved rounds, median of 3 x 6 steps.
-usage: python tools/ab_schedule.py [fp32|bf16] [bnsums|joins|defer|prio]   (defer: layers.SCHED.defer_residual on / off; joins: which join outputs are also written as planes; bnsums: the default schedule and the one-stream order with the batch-norm
+usage: python tools/ab_schedule.py [fp32|bf16] [bnsums|joins|defer|prio|tapskip]   (tapskip: the default schedule with the conv tile kernel's tap lists and by-depth frames on / off (RCF_CONV_NO_TAP_SKIP); defer: layers.SCHED.defer_residual on / off; joins: which join outputs are also written as planes; bnsums: the default schedule and the one-stream order with the batch-norm
 backward sums from the data gradients' epilogues (layers.SCHED.fuse_bn_bwd) on and off)"""
 import os, sys, time, types
 import numpy as np
@@ -45,6 +45,10 @@ if joins:
     # the last stage's output for the decode heads; default schedule
     configs = {f"joins {j}, heads {'on' if h else 'off'}": (True, True, True, layers.SCHED.fuse_bn_bwd, j, h)
                for j in ("all", "stage") for h in (True, False)}
+tapskip = len(sys.argv) > 2 and sys.argv[2] == "tapskip"
+if tapskip:
+    configs = {f"default schedule, {'tap lists' if on else 'RCF_CONV_NO_TAP_SKIP'}":
+               (layers.SCHED.overlap_wgrad, layers.SCHED.late_wgrad, layers.SCHED.planes, layers.SCHED.fuse_bn_bwd, on) for on in (True, False)}
 for _ in range(4):
     tr.step(batch)
 res = {k: [] for k in configs}
@@ -52,7 +56,10 @@ for r in range(int(os.environ.get("AB_ROUNDS", "3"))):
     for name, cfg in configs.items():
         ov, late, planes, fuse = cfg[:4]
         layers.SCHED.overlap_wgrad, layers.SCHED.late_wgrad, layers.SCHED.planes, layers.SCHED.fuse_bn_bwd = ov, late, planes, fuse
-        if prio:
+        if tapskip:
+            torch.cuda.synchronize()
+            rcf_amd.ops.set_conv_flags(0 if cfg[4] else rcf_amd._lib.CONV_NO_TAP_SKIP)
+        elif prio:
             torch.cuda.synchronize()
             layers.SCHED.side_priority = int(cfg[4])
             layers._side_streams.clear()
