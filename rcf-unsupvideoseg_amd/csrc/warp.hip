@@ -331,14 +331,21 @@ __device__ __forceinline__ Tap4 border_tap(int x, int y, float fx, float fy, con
     const v2f d = {g.dx, g.dy}, r = {g.rx, g.ry};
     const v2f p = {(float)x + fx, (float)y + fy};
     // norm_grid: 2*p/(size-1) - 1;  grid_sampler_unnormalize(align_corners=True): ((g+1)/2)*(size-1)
-    const v2f t = 2.0f * p;
+    // 2 p overflows for |p| > 1.7e38 and for an infinite flow; q and the residual below would be inf - inf = NaN, which the clip
+    // sends to 0 where +inf belongs at size - 1 (make_taps, torch).  Clamped to +-3e38 the arithmetic stays finite and clips to the
+    // right side; a NaN leaves v_med3_f32 as NaN or as the smaller bound and lands on 0 either way.  Every 2 p that does not
+    // clip (|2 p| <= 3e38) keeps its bits.
+    v2f t = 2.0f * p;
+    t.x = __builtin_amdgcn_fmed3f(t.x, -3e38f, 3e38f);
+    t.y = __builtin_amdgcn_fmed3f(t.y, -3e38f, 3e38f);
     v2f q = t * r;
     q = __builtin_elementwise_fma(__builtin_elementwise_fma(-q, d, t), r, q);        // == t / d, correctly rounded
     const v2f gn = q - 1.0f;
     v2f i = ((gn + 1.f) * 0.5f) * d;
-    // clip_coordinates: below 0 (or NaN) -> 0, above size-1 -> size-1
-    i.x = fminf(fmaxf(i.x, 0.f), g.dx);
-    i.y = fminf(fmaxf(i.y, 0.f), g.dy);
+    // clip_coordinates: below 0 (or NaN) -> 0, above size-1 -> size-1.  One v_med3_f32 (a NaN operand makes it the minimum of the
+    // other two, 0) instead of max + min: with the clamp above, the instruction count of the position arithmetic is unchanged
+    i.x = __builtin_amdgcn_fmed3f(i.x, 0.f, g.dx);
+    i.y = __builtin_amdgcn_fmed3f(i.y, 0.f, g.dy);
     v2f f = {floorf(i.x), floorf(i.y)};
     v2f w = i - f;
     int x0 = (int)f.x, y0 = (int)f.y;
@@ -628,7 +635,8 @@ extern "C" int rcf_warp_l1_residual_f32(const float *im1, const float *im2, cons
                                         double *out, int B, int C, int H, int W, int pad_mode, void *stream) {
     const bool per_pixel = pad_mode & RCF_WARP_PER_PIXEL;
     pad_mode &= ~RCF_WARP_PER_PIXEL;
-    if (!im1 || !im2 || !flow || !out || B <= 0 || C <= 0 || H < 2 || W < 2) return RCF_EINVAL;
+    if (!im1 || !im2 || !flow || !out || B <= 0 || C <= 0 || H < 2 || W < 2 || (pad_mode != 0 && pad_mode != 1)) return RCF_EINVAL;
+    if ((long)H * W >= (1L << 30)) return RCF_EINVAL;           // the kernels hold H * W in an int
     hipStream_t st = rcf_stream(stream);
     hipError_t e = hipMemsetAsync(out, 0, 2 * sizeof(double), st);
     if (e != hipSuccess) return (int)e;
