@@ -742,6 +742,28 @@ int rcf_aug_flows_f32(const float *flows, int B, int K, int H, int W, const rcf_
 int rcf_aug_masks_u8(const uint8_t *masks, int B, int K, int H, int W, const rcf_aug_params *params, float *out, int oh,
                      int ow, void *stream);
 
+/* ---- Pillow's 8-bit resampler + IoU counts (tools/STv2-FBMS59-evaluation/eval_tool.py; csrc/pil_resample.hip) ----------
+ * Image.resize of N u8 planes [h][w] to [H][W] with Pillow's integer arithmetic (libImaging/Resample.c, 8 bits per channel): a
+ * horizontal and then a vertical pass, each out = clip(((1 << 21) + sum_j k[i][j] in[first_i + j]) >> 22, 0, 255) in int32, the
+ * horizontal result rounded to u8 before the vertical pass.  The tables carry the filter and the scale (rcf_amd.pilresize
+ * .coeff_tables transcribes Pillow's): kx int32 [W][ksx] with bx int32 [W][2] = (first tap, tap count <= ksx) per output column,
+ * ky [H][ksy] / by [H][2] per output row; taps must lie inside the frame (ranges are clamped, a malformed table gives a wrong
+ * picture and no access outside src).  kx == NULL: no horizontal pass (needs W == w), ky == NULL: no vertical pass (H == h), as
+ * Pillow skips the pass of an axis that keeps its size.  src: element (n, y, x) at src[((n h + y) w + x) pix_stride]:
+ * pix_stride 1 = packed L planes, 3 = channel 0 of interleaved RGB read in place.
+ * dst (may be NULL): u8 [N][H][W].  counts (may be NULL): int64 [N][2], zero-filled by the caller, += (intersection, union) of
+ * (resized >= pred_min) and (gt != 0) with gt u8 [N][H][W]; 0 <= pred_min <= 256.  Integer atomics: order-independent.
+ * RCF_EINVAL before any launch: a NULL src, sizes <= 0, pix_stride not 1 or 3, neither dst nor counts, counts without gt, a table
+ * without its bounds or tap count, a missing table on an axis that changes size, ksy > RCF_PIL_MAX_TAPS (the source rows of
+ * one output row no longer fit the kernel's LDS window; bicubic: a reduction beyond 63 x).  Nothing allocates.
+ * rcf_pil_resample_tile_rows: the output rows per block the launch uses for (h, H, ksy) -- 32, 16, ..., 1, the tallest tile whose
+ * source rows fit the window; ksy = 0: no vertical pass; 0 when the call would be refused.  A pure function. */
+#define RCF_PIL_MAX_TAPS 256
+int rcf_pil_resample_tile_rows(int h, int H, int ksy);
+int rcf_pil_resample_u8(const uint8_t *src, int N, int h, int w, int pix_stride, const int32_t *kx, const int32_t *bx, int ksx,
+                        const int32_t *ky, const int32_t *by, int ksy, int H, int W, uint8_t *dst, const uint8_t *gt,
+                        int pred_min, long long *counts, void *stream);
+
 /* ---- DINO ViT forward + soft NCut -----------------------------------------
  * models/dino_vit.py:110-167,176-276 (nn.Linear / attention products, LayerNorm eps 1e-6, softmax, GELU) and
  * tools/SemanticConstraintsAndMAA/semantic_constraints.py:21-75 (soft NCut value, Adam refinement of the mask). */

@@ -246,6 +246,8 @@ PROTOS = {
     "rcf_fold_bwd_prepare_f32": (c_int, [P] * 6 + [c_double] + [P] * 9 + [c_size_t, c_int, c_int, P]),
     "rcf_eval_iou_counts_f32": (c_int, [P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_float, P, P]),
     "rcf_davis_counts_u8": (c_int, [P, P, P, c_int, c_int, c_int, c_int, P, P]),
+    "rcf_pil_resample_tile_rows": (c_int, [c_int, c_int, c_int]),
+    "rcf_pil_resample_u8": (c_int, [P, c_int, c_int, c_int, c_int, P, P, c_int, P, P, c_int, c_int, c_int, P, P, c_int, P, P]),
     "rcf_aug_frames_u8": (c_int, [P, c_int, c_int, c_int, c_int, P, P, c_int, c_int, P, P, P]),
     "rcf_aug_flows_f32": (c_int, [P, c_int, c_int, c_int, c_int, P, P, c_int, c_int, P]),
     "rcf_aug_masks_u8": (c_int, [P, c_int, c_int, c_int, c_int, P, P, c_int, c_int, P]),

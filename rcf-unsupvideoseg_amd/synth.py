@@ -403,6 +403,76 @@ def maa_tree(root, seed=77, step=0):
     return root, os.path.join(root, "data")
 
 
+# ---- SegTrackv2 / FBMS59 evaluation (rcf_amd.stv2_fbms) ---------------------------------------------------------------------
+# (dataset, sequence, frames, export size, annotation size, prediction mode, annotation mode): both directions of the
+# resize, one sequence with equal sizes, one with a single axis differing, one L export, one RGB annotation
+STV2_FBMS_TREE = (
+    ("SegTrackv2", "birdfall", 4, (48, 80), (97, 150), "RGB", "L"),        # enlargement, odd target
+    ("SegTrackv2", "frog", 3, (120, 200), (45, 67), "RGB", "L"),           # reduction
+    ("SegTrackv2", "worm", 5, (60, 90), (60, 90), "L", "L"),               # equal sizes, L export
+    ("FBMS59", "cats01", 5, (64, 96), (64, 130), "RGB", "L"),              # one axis only
+    ("FBMS59", "dogs02", 4, (50, 70), (121, 161), "RGB", "RGB"),           # enlargement, RGB annotation
+    ("FBMS59", "marple7", 3, (90, 140), (40, 131), "RGB", "L"),            # reduction of one axis, mild one of the other
+)
+STV2_FBMS_LISTS = {"SegTrackv2": ("data_SegTrackv2", "trainval.txt"), "FBMS59": ("data_fbms59", "val_all.txt")}
+STV2_FBMS_EMPTY = {("frog", 1), ("cats01", 3)}          # (sequence, frame): prediction and annotation both empty -> IoU nan
+STV2_FBMS_UNANNOTATED = {("cats01", 1), ("dogs02", 0), ("dogs02", 2), ("marple7", 2)}   # FBMS59 frames without annotation
+
+
+def _stv2_fbms_soft(g, H, W):
+    """u8 [H,W]: a shallow cone around an ellipse with a sawtooth ripple -- most of the frame lies within a few grey levels of
+    the evaluator's threshold (89 / 90), so one wrong rounding in the resize flips pixels.  Only + - * / sqrt and fmod: the
+    same bytes on every machine."""
+    yy, xx = np.meshgrid(np.arange(H, dtype=np.float64), np.arange(W, dtype=np.float64), indexing="ij")
+    cy, cx = g.uniform(0.35, 0.65) * H, g.uniform(0.35, 0.65) * W
+    ry, rx = g.uniform(0.2, 0.3) * H, g.uniform(0.2, 0.3) * W
+    d = np.sqrt(((yy - cy) / ry) ** 2 + ((xx - cx) / rx) ** 2)
+    period = g.uniform(5.0, 9.0)
+    saw = np.abs(np.fmod(xx * g.uniform(0.6, 1.0) + yy * g.uniform(0.6, 1.0), period) / period - 0.5)
+    v = 89.5 + 8.0 * (1.0 - d) + 9.0 * (saw - 0.25)
+    return np.clip(np.floor(v + 0.5), 0, 255).astype(np.uint8), (cy, cx, ry, rx)
+
+
+def stv2_fbms_tree(root, seed=59, step=0):
+    """A synthetic tree for both datasets of rcf_amd.stv2_fbms under `root`, laid out as the reference's eval_tool.py reads it
+    from its working directory: root/data/data_SegTrackv2/trainval.txt and root/data/data_fbms59/val_all.txt with lines
+    `JPEGImages/<seq>/ 00000.jpg 00001.jpg ...`, annotations under .../Annotations/<seq>/ (u8 0 / 255; SegTrackv2 under the
+    frame's own name -- a PNG stream whatever the name says, Pillow opens by content --, FBMS59 as .png and missing for the
+    frames of STV2_FBMS_UNANNOTATED) and the exported masks root/pred/<dataset>/pred_seg_{seq}_{frame:05}_{step:07}.png.
+    Returns (root/data, {dataset: prediction directory})."""
+    import os
+    from PIL import Image
+    g = _rng(seed)
+    data = os.path.join(root, "data")
+    pred_dirs = {ds: os.path.join(root, "pred", ds) for ds in STV2_FBMS_LISTS}
+    lines = {ds: [] for ds in STV2_FBMS_LISTS}
+    for d in pred_dirs.values():
+        os.makedirs(d, exist_ok=True)
+    for ds, seq, T, (h, w), (H, W), pmode, amode in STV2_FBMS_TREE:
+        ann_dir = os.path.join(data, STV2_FBMS_LISTS[ds][0], "Annotations", seq)
+        os.makedirs(ann_dir, exist_ok=True)
+        lines[ds].append(f"JPEGImages/{seq}/ " + " ".join(f"{t:05d}.jpg" for t in range(T)) + "\n")
+        for t in range(T):
+            p, (cy, cx, ry, rx) = _stv2_fbms_soft(g, h, w)
+            yy, xx = np.meshgrid(np.arange(H, dtype=np.float64), np.arange(W, dtype=np.float64), indexing="ij")
+            sy, sx = g.uniform(-0.1, 0.1) * H, g.uniform(-0.1, 0.1) * W           # the annotation: that ellipse, shifted
+            a = (((yy - cy * H / h - sy) / (ry * H / h)) ** 2 + ((xx - cx * W / w - sx) / (rx * W / w)) ** 2 < 1.0)
+            a = a.astype(np.uint8) * 255
+            if (seq, t) in STV2_FBMS_EMPTY:
+                p[:], a[:] = 0, 0
+            pim = Image.fromarray(p if pmode == "L" else np.stack([p, p, p], -1))
+            pim.save(os.path.join(pred_dirs[ds], f"pred_seg_{seq}_{t:05d}_{step:07}.png"))
+            if ds == "FBMS59" and (seq, t) in STV2_FBMS_UNANNOTATED:
+                continue
+            aim = Image.fromarray(a if amode == "L" else np.stack([a, a // 2, 255 - a], -1))
+            name = f"{t:05d}.png" if ds == "FBMS59" else f"{t:05d}.jpg"
+            aim.save(os.path.join(ann_dir, name), format="PNG")
+    for ds, (sub, name) in STV2_FBMS_LISTS.items():
+        with open(os.path.join(data, sub, name), "w") as f:
+            f.writelines(lines[ds])
+    return data, pred_dirs
+
+
 def fill_state_dict(shapes, seed=7, bn3_gamma=0.5, seg_scale=10.0):
     """Seeded weights for every entry of a state-dict `shapes` mapping name -> shape.
 
