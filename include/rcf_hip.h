@@ -553,6 +553,25 @@ int rcf_warp_l1_residual_f32(const float *im1, const float *im2, const float *fl
 int rcf_photometric_loss_f32(const float *im, const float *recon, const float *occ, float w_l1, float w_ssim,
                              float *out, double *scratch, int B, int C, int H, int W, void *stream);
 
+/* ---- PWC-Lite cost volume (models/amd/correlation_native.py:6-23; csrc/correlation.hip) ----------------------------------
+ * d = max_disp (1..4; PWC-Lite: 4), D = 2 d + 1, x1 / x2 f32 [B][C][H][W], out / dout f32 [B][D D][H][W]:
+ *   corr[b, i D + j, y, x] = (1/C) sum_c x1[b,c,y,x] x2z[b,c, y+i-d, x+j-d]     i, j in 0..D-1, the row displacement i outermost
+ *   out = corr where slope == 1, else corr > 0 ? corr : slope corr              (the LeakyReLU(0.1) of pwc_lite.py:202-203, fused)
+ * x2z is x2 with real zeros outside the image, as F.pad makes them: the zeros are multiplied, not skipped (an infinite x1 against
+ * a tap outside the image gives NaN; a NaN in x2 reaches exactly the (i, j, y, x) whose tap is that pixel).
+ * Backward, with g = dout where slope == 1, else dout (out > 0 ? 1 : slope) for the caller's `out` (may be NULL iff slope == 1):
+ *   dx1[b,c,y,x] = (1/C) sum_ij g[b, i D + j, y, x]         x2z[b,c, y+i-d, x+j-d]
+ *   dx2[b,c,y,x] = (1/C) sum_ij g[b, i D + j, y-i+d, x-j+d] x1[b,c, y-i+d, x-j+d]   (terms whose source pixel is outside the image drop)
+ * dx1 / dx2 (either may be NULL, not both) are OVERWRITTEN.  Every sum runs in one thread in a fixed order: no atomics, results
+ * are bit-reproducible.  RCF_EINVAL before any launch -- sizes and ranges first, then pointers: a size <= 0, max_disp outside
+ * 1..4, a tensor of 2^31 elements or more; a NULL operand, both gradients NULL, slope != 1 without out.
+ * rcf_correlation_geometry: 0 -> rows, 1 -> columns of a workgroup's pixel tile, 2 -> channels staged per trip; 0 otherwise. */
+int rcf_correlation_geometry(int which);
+int rcf_correlation_fwd_f32(const float *x1, const float *x2, float *out, int B, int C, int H, int W, int max_disp, float slope,
+                            void *stream);
+int rcf_correlation_bwd_f32(const float *x1, const float *x2, const float *dout, const float *out, float *dx1, float *dx2, int B,
+                            int C, int H, int W, int max_disp, float slope, void *stream);
+
 /* ---- dense CRF (permutohedral mean-field) -------------------------------------------------------
  * Replaces torchcrf_cpp.crf_soft / crf_hard (tools/torchCRF/src/torchcrf.cu:106-149), batched over
  * frames, persistent caller-owned workspace instead of 12 cudaMalloc/cudaFree per frame.

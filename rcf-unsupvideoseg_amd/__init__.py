@@ -8,6 +8,7 @@ __version__ = "0.1.0"
 
 from . import _lib, data_pipeline, davis, evaluate, maa, ncut, offline, ops, semantic, synth, vit  # noqa: F401
 from .backbone import FCNHead, ResNet  # noqa: F401
+from .correlation import Correlation  # noqa: F401
 from .evaluate import Evaluator  # noqa: F401
 from .crf import CRFHead, crf_hard, crf_soft  # noqa: F401
 from .flow_head import CompactnessHead, FlowAggregationHeadWithResidual  # noqa: F401

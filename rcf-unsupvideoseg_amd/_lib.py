@@ -178,6 +178,9 @@ PROTOS = {
     "rcf_occu_mask_bidirection_f32": (c_int, [P, P, P, c_float, c_float, c_int, c_int, c_int, P]),
     "rcf_warp_l1_residual_f32": (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, P]),
     "rcf_photometric_loss_f32": (c_int, [P, P, P, c_float, c_float, P, P, c_int, c_int, c_int, c_int, P]),
+    "rcf_correlation_geometry": (c_int, [c_int]),
+    "rcf_correlation_fwd_f32": (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_int, c_float, P]),
+    "rcf_correlation_bwd_f32": (c_int, [P, P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_float, P]),
     "rcf_crf_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "rcf_crf_soft": (c_int, [P, P, c_int, c_int, c_int, c_float, c_float, c_float, c_float, c_float, c_int, P, P, P,
                              P, c_size_t, P]),

@@ -1030,6 +1030,42 @@ def photometric_loss(im, recon, occ, w_l1=0.15, w_ssim=0.85):
     return out[0]
 
 
+def _correlation_operands(*ts):
+    _need_cuda(*ts)
+    for t in ts:
+        if t is not None and t.dtype != torch.float32:
+            raise _lib.RcfHipError(f"the cost volume takes float32 tensors, not {t.dtype}")
+    if ts[0].dim() != 4 or ts[0].shape != ts[1].shape:
+        raise _lib.RcfHipError(f"x1 and x2 must share one [B, C, H, W] shape: {tuple(ts[0].shape)}, {tuple(ts[1].shape)}")
+
+
+def correlation(x1, x2, max_displacement=4, slope=1.0):
+    """PWC-Lite's cost volume (models/amd/correlation_native.py): [B, (2 d + 1)^2, H, W], the mean over the channels of x1 times x2
+    shifted by (i - d, j - d), i outermost; slope != 1 applies LeakyReLU(slope) in the same pass (include/rcf_hip.h)"""
+    _correlation_operands(x1, x2)
+    x1, x2 = x1.contiguous(), x2.contiguous()
+    B, C, H, W = x1.shape
+    D = 2 * int(max_displacement) + 1
+    out = torch.empty((B, D * D, H, W), dtype=torch.float32, device=x1.device)
+    call("rcf_correlation_fwd_f32", _p(x1), _p(x2), _p(out), B, C, H, W, int(max_displacement), float(slope), _stream())
+    return out
+
+
+def correlation_bwd(x1, x2, dout, out=None, max_displacement=4, slope=1.0, need_dx1=True, need_dx2=True):
+    """-> (dx1, dx2), None for the one not asked for; `out` (the forward's result) is needed when slope != 1"""
+    _correlation_operands(x1, x2, dout, out)
+    x1, x2, dout = x1.contiguous(), x2.contiguous(), dout.contiguous()
+    B, C, H, W = x1.shape
+    D = 2 * int(max_displacement) + 1
+    if any(t is not None and tuple(t.shape) != (B, D * D, H, W) for t in (dout, out)):
+        raise _lib.RcfHipError(f"dout and out must be [B, {D * D}, H, W] for x1 of shape {tuple(x1.shape)}")
+    dx1 = torch.empty_like(x1) if need_dx1 else None
+    dx2 = torch.empty_like(x2) if need_dx2 else None
+    call("rcf_correlation_bwd_f32", _p(x1), _p(x2), _p(dout), _p(out.contiguous() if out is not None else None), _p(dx1), _p(dx2),
+         B, C, H, W, int(max_displacement), float(slope), _stream())
+    return dx1, dx2
+
+
 # ------------------------------------------------------------------------------- optimiser
 def adam_step(param, grad, exp_avg, exp_avg_sq, lr, step, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0,
               grad_scale=1.0):
