@@ -158,9 +158,38 @@ typedef struct {
     int y0, x0, h, w;     /* rectangle */
     int band;             /* 0: the whole rectangle; t > 0: only its border frame of thickness t (2t < h, w) */
 } rcf_conv_region;
-/* Which kernel family a forward (dgrad = 0) / data-gradient (dgrad = 1) launch with this shape, these operand pointers and
- * flags takes: 0 the fp32-MFMA kernels, 1 the 128 x 256-tile family, 2 conv_h2p_kernel.  A pure function of its arguments --
- * nothing is launched, no state is read (profiling labels). */
+/* What a conv launch with this shape, these operand pointers (which of them are NULL: none is read) and these flags will run: the
+ * library's own launch plan, the one value its entry points consume.  direction: 0 forward, 1 data gradient, 2 weight gradient;
+ * storage: RCF_F32 (rcf_conv2d_*_f32) or RCF_BF16 (rcf_conv2d_*_bf16).  Returns 0, or the status with which the launch itself is
+ * refused.  A pure function of its arguments: nothing is launched, no state is read.  It answers for the GEMM kernels; the thin
+ * 1x1 convs (<= 16 output channels) that the fp32 entry points hand to their streaming passes are not marked.
+ *   kernel (forward / data gradient)          kernel (weight gradient)
+ *   0 RCF_KERNEL_MFMA  igemm_conv_kernel        16 RCF_KERNEL_WGRAD_MFMA      igemm_wgrad_kernel (fp32 MFMA)
+ *   1 RCF_KERNEL_TILE  igemm_conv_x3_kernel     17 RCF_KERNEL_WGRAD_X3        igemm_wgrad_x3_kernel
+ *   2 RCF_KERNEL_H2P   conv_h2p_kernel          18 RCF_KERNEL_WGRAD_X3_WIDE   igemm_wgrad_x3_wide_kernel
+ *   3 RCF_KERNEL_H2D   conv_h2d_kernel          19 RCF_KERNEL_WGRAD_H2T       igemm_wgrad_h2t_kernel
+ *   4 RCF_KERNEL_BF16  conv_bf16_kernel         20 RCF_KERNEL_WGRAD_H2D       igemm_wgrad_h2d_kernel (x and dy as pair planes)
+ *                                               21 RCF_KERNEL_WGRAD_BF16      wgrad_bf16_kernel
+ *                                               22 RCF_KERNEL_WGRAD_BF16_DMA  wgrad_bf16_dma_kernel
+ * tile_rows x tile_cols: the output tile of one workgroup (conv_h2p_kernel: the 32-row blocks it walks); splitk: workgroups that
+ * share one tile of a weight gradient (1 otherwise). */
+#define RCF_KERNEL_MFMA 0
+#define RCF_KERNEL_TILE 1
+#define RCF_KERNEL_H2P 2
+#define RCF_KERNEL_H2D 3
+#define RCF_KERNEL_BF16 4
+#define RCF_KERNEL_WGRAD_MFMA 16
+#define RCF_KERNEL_WGRAD_X3 17
+#define RCF_KERNEL_WGRAD_X3_WIDE 18
+#define RCF_KERNEL_WGRAD_H2T 19
+#define RCF_KERNEL_WGRAD_H2D 20
+#define RCF_KERNEL_WGRAD_BF16 21
+#define RCF_KERNEL_WGRAD_BF16_DMA 22
+typedef struct { int kernel, tile_rows, tile_cols, splitk; } rcf_conv_plan;
+int rcf_conv_plan_of(const rcf_conv_shape *s, const rcf_conv_region *region, int direction /* 0 fwd, 1 dgrad, 2 wgrad */,
+                     int storage /* RCF_F32, RCF_BF16 */, rcf_conv_plan *out);
+/* rcf_conv_plan_of(s, region, dgrad ? 1 : 0, RCF_F32).kernel, or its status where that launch is refused; RCF_EWORKSPACE for a data
+ * gradient whose weights are not prepared (it needs a workspace, and this query has none to offer) */
 int rcf_conv_kernel_of(const rcf_conv_shape *s, const rcf_conv_region *region, int dgrad);
 int rcf_conv2d_fwd_region_f32(const float *x, const float *w, const float *bias, float *y, const rcf_conv_shape *s,
                               const rcf_conv_region *region, int act, float slope, int beta, void *stream);

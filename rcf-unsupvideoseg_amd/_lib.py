@@ -78,6 +78,17 @@ class ConvRegion(ctypes.Structure):
     _fields_ = [(n, c_int) for n in ("y0", "x0", "h", "w", "band")]
 
 
+class ConvPlan(ctypes.Structure):
+    """mirror of rcf_conv_plan (rcf_conv_plan_of)"""
+    _fields_ = [(n, c_int) for n in ("kernel", "tile_rows", "tile_cols", "splitk")]
+
+
+# rcf_conv_plan.kernel (include/rcf_hip.h RCF_KERNEL_*)
+KERNEL_MFMA, KERNEL_TILE, KERNEL_H2P, KERNEL_H2D, KERNEL_BF16 = 0, 1, 2, 3, 4
+KERNEL_WGRAD_MFMA, KERNEL_WGRAD_X3, KERNEL_WGRAD_X3_WIDE, KERNEL_WGRAD_H2T, KERNEL_WGRAD_H2D = 16, 17, 18, 19, 20
+KERNEL_WGRAD_BF16, KERNEL_WGRAD_BF16_DMA = 21, 22
+
+
 class FlowHeadCfg(ctypes.Structure):
     """mirror of rcf_flowhead_cfg"""
     _fields_ = [(n, c_int) for n in ("B", "C", "h", "w", "logits_pitch", "nf", "D", "robust", "tanh_residual")] + \
@@ -138,6 +149,7 @@ PROTOS = {
     "rcf_conv_weight_pairs2_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
     "rcf_conv_weight_pairs2_f32": (c_int, [P, c_int, c_int, c_int, c_int, c_int, P, P, c_uint, P]),
     "rcf_conv_kernel_of": (c_int, [_CS, _CR, c_int]),
+    "rcf_conv_plan_of": (c_int, [_CS, _CR, c_int, c_int, ctypes.POINTER(ConvPlan)]),
     "rcf_conv_pairs2_useful": (c_int, [c_int, c_int, c_int, c_int, c_int]),
     "rcf_conv_weights_prepare_f32": (c_int, [P, c_int, P, c_int, P, c_int, c_int, P, c_uint, P]),
     "rcf_conv_weights_prepare_bf16": (c_int, [P, c_int, P, c_int, c_int, c_uint, P]),

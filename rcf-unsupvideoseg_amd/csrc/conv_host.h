@@ -1,5 +1,6 @@
 // Host-side launch helpers shared by the conv entry points of csrc/igemm_conv.hip (fp32 tensors) and csrc/igemm_bf16.hip
-// (16-bit tensors): shape and region checks, region -> kernel parameters, the split-K plan of the weight gradients.
+// (16-bit tensors): shape and region checks, region -> kernel parameters, and what the weight-gradient planners of the two files
+// (plan_wgrad: their cost models differ) literally share -- the split-K search and tail, the one-tap rule, the launch parameters.
 // No device code; included by those two files only.
 #pragma once
 #include <math.h>
@@ -71,4 +72,41 @@ static inline long splitk_chunk_fit(long chunk, long unit, long RR, const rcf_co
     while (chunk > unit && ((chunk / RR + 2) * img_bytes >= (1L << 31) || (chunk / RR + 2) * dy_bytes >= (1L << 31)))
         chunk = (chunk / 2 + unit - 1) / unit * unit;
     return chunk;
+}
+
+// The tail of both weight-gradient planners (PL = the file's WgradPlan, with mr / nr / itiles / jtiles set): `sk` splits of the M
+// pixels in chunks of whole K-steps (`unit` pixels; `fit`: halved until 32-bit offsets reach, splitk_chunk_fit), and the column
+// tiles of one tap -- onetap: a tile's 64 nr columns lie inside one tap; cblocks > 0: tiles numbered channel-block-major
+// (rcf_common.h rcf_wgrad_tile_ij).
+template <class PL>
+static inline void wgrad_plan_tail(PL &pl, const rcf_conv_shape *s, long M, long RR, long sk, long unit, bool fit, int esize) {
+    long chunk = ((M + sk - 1) / sk + unit - 1) / unit * unit;
+    if (fit) chunk = splitk_chunk_fit(chunk, unit, RR, s, esize);
+    pl.chunk = chunk;
+    pl.splitk = (int)((M + chunk - 1) / chunk);
+    pl.onetap = s->Cin % (64 * pl.nr) == 0;
+    pl.cblocks = pl.onetap && s->R * s->S > 1 && !(s->flags & RCF_CONV_NO_WGRAD_XCD) ? s->Cin / (64 * pl.nr) : 0;
+}
+
+// KERNEL<ARGS..., B> / KERNEL<ARGS..., B1, B2> picked by run-time flags, through the including file's RCF_GO(kernel) launch macro
+#define RCF_GO_B(b, KERNEL, ...) do { if (b) RCF_GO(KERNEL<__VA_ARGS__, true>); else RCF_GO(KERNEL<__VA_ARGS__, false>); } while (0)
+#define RCF_GO_BB(b1, b2, KERNEL, ...) \
+    do { if (b1) RCF_GO_B(b2, KERNEL, __VA_ARGS__, true); else RCF_GO_B(b2, KERNEL, __VA_ARGS__, false); } while (0)
+
+static inline size_t wgrad_workspace_bytes(int splitk, const rcf_conv_shape *s) {    // the split-K partial results
+    return splitk <= 1 ? 0 : (size_t)splitk * s->Cout * s->R * s->S * s->Cin * sizeof(float);
+}
+
+// the launch parameters both weight gradients fill the same way (P = the file's WgradParams; X, DY and its own fields: the caller)
+template <class P, class PL>
+static inline void fill_wgrad(P &p, const PL &pl, const rcf_conv_shape *s, const rcf_conv_region *r, int beta, float *dw, void *workspace) {
+    p.OUT = pl.splitk > 1 ? (float *)workspace : dw;
+    p.Cout = s->Cout; p.Cin = s->Cin; p.R = s->R; p.S = s->S;
+    p.H = s->H; p.W = s->W; p.Ho = s->Ho; p.Wo = s->Wo; p.stride = s->stride; p.pad = s->pad; p.dil = s->dil;
+    p.x_pitch = s->x_pitch; p.dy_pitch = s->y_pitch;
+    fill_region(p, r, s->N, s->Ho, s->Wo);
+    p.chunk = pl.chunk; p.itiles = pl.itiles; p.jtiles = pl.jtiles;
+    p.split_stride = (long)s->Cout * s->R * s->S * s->Cin; p.beta = beta;
+    p.xcd_map = (s->flags & RCF_CONV_NO_WGRAD_XCD) ? 0 : 1;
+    p.cblocks = pl.cblocks;
 }

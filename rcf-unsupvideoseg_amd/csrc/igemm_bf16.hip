@@ -1238,7 +1238,7 @@ void launch_cfg(ConvParams &p, bool strided, bool dgrad, hipStream_t st, int ep)
     else hipLaunchKernelGGL((conv_bf16_kernel<MR, NR, WM, WN, false, false, OBF, true, 3, 1>), grid, dim3(64 * WM * WN), 0, st, p);
 }
 
-// column-tile width launch_conv picks for Ncol output columns
+// column-tile width of a launch with Ncol output columns (launch_conv, rcf_conv_plan_bf16)
 inline int conv_bn_of(int Ncol) { return Ncol <= 64 ? 64 : (Ncol <= 128 ? 128 : 256); }
 
 template <bool OBF>
@@ -1260,24 +1260,51 @@ int launch_conv(ConvParams &p, bool dgrad, hipStream_t st, int ep = 0) {
     p.b_bytes = (int)bbytes;
     const bool strided = p.div > 1;
     if (ep && (strided || !OBF || p.Ncol % conv_bn_of(p.Ncol) || p.bias || p.act)) return RCF_EINVAL;
-    if (p.Ncol <= 64) launch_cfg<2, 1, 2, 2, OBF>(p, strided, dgrad, st, ep);
-    else if (p.Ncol <= 128) launch_cfg<2, 2, 2, 2, OBF>(p, strided, dgrad, st, ep);
-    else launch_cfg<2, 4, 2, 2, OBF>(p, strided, dgrad, st, ep);
+    switch (conv_bn_of(p.Ncol)) {
+        case 64: launch_cfg<2, 1, 2, 2, OBF>(p, strided, dgrad, st, ep); break;
+        case 128: launch_cfg<2, 2, 2, 2, OBF>(p, strided, dgrad, st, ep); break;
+        default: launch_cfg<2, 4, 2, 2, OBF>(p, strided, dgrad, st, ep);
+    }
     RCF_LAUNCH_CHECK();
     return 0;
 }
 
+// the GEMM view of a forward (x -> y) or data-gradient (dy -> dx) launch, rows restricted to `region`: everything but the operands
+// and the epilogue.  Returns 0 / RCF_EINVAL.
+int conv_geometry(ConvParams &p, const rcf_conv_shape *s, const rcf_conv_region *region, bool dgrad) {
+    p.flags = s->flags;
+    p.S = s->S;
+    if (dgrad) {
+        p.Ncol = s->Cin; p.K = s->R * s->S * s->Cout;
+        p.Ho = s->H; p.Wo = s->W; p.Hs = s->Ho; p.Ws = s->Wo; p.Cs = s->Cout;
+        p.up = 1; p.off = s->pad; p.step = -s->dil; p.div = s->stride;
+        p.a_pitch = s->y_pitch; p.a_img_stride = (long)s->Ho * s->Wo * s->y_pitch; p.y_pitch = s->x_pitch;
+    } else {
+        p.Ncol = s->Cout; p.K = s->R * s->S * s->Cin;
+        p.Ho = s->Ho; p.Wo = s->Wo; p.Hs = s->H; p.Ws = s->W; p.Cs = s->Cin;
+        p.up = s->stride; p.off = -s->pad; p.step = s->dil; p.div = 1;
+        p.a_pitch = s->x_pitch; p.a_img_stride = (long)s->H * s->W * s->x_pitch; p.y_pitch = s->y_pitch;
+    }
+    return set_region(p, region, s->N, p.Ho, p.Wo);
+}
+
+enum WgradKernel { WG_BF16 = RCF_KERNEL_WGRAD_BF16, WG_BF16_DMA = RCF_KERNEL_WGRAD_BF16_DMA };
 struct WgradPlan {
+    WgradKernel kernel;
     int mr, nr, itiles, jtiles, splitk;
     long chunk;
+    bool onetap;    // conv_host.h wgrad_plan_tail
+    int cblocks;
 };
+// tiles, split factor and kernel of a weight gradient (every checked shape has a kernel here)
 WgradPlan plan_wgrad(const rcf_conv_shape *s, const rcf_conv_region *reg) {
-    WgradPlan pl;
+    WgradPlan pl{};
     const int ktot = s->R * s->S * s->Cin;
     pl.nr = ktot >= 256 ? 4 : (ktot >= 128 ? 2 : 1);
     // 64 output channels take the 128-row LDS-DMA kernel too when the columns allow it: these layers are bound by memory,
     // not by the half-empty tile rows (layer1 3x3 64->64: 0.104 -> 0.093 ms, 1x1 256->64: 0.089 -> 0.068)
     pl.mr = (s->Cout > 64 || (s->Cout == 64 && pl.nr >= 2)) ? 2 : 1;
+    pl.kernel = (pl.mr == 2 && pl.nr >= 2) ? WG_BF16_DMA : WG_BF16;
     pl.itiles = rcf_cdiv(s->Cout, 64 * pl.mr);
     pl.jtiles = rcf_cdiv(ktot, 64 * pl.nr);
     const long RR = region_pixels(reg, s->Ho, s->Wo);
@@ -1289,9 +1316,7 @@ WgradPlan plan_wgrad(const rcf_conv_shape *s, const rcf_conv_region *reg) {
     const double px_us = 0.025 * fmax((double)(pl.mr * pl.nr) / 8.0, 0.35);
     const long maxsk = M / 512 > 1 ? M / 512 : 1;
     const long sk = splitk_search(tiles, M, 512, maxsk < 256 ? maxsk : 256, px_us, (double)s->Cout * ktot * 4.0);
-    const long chunk = splitk_chunk_fit(((M + sk - 1) / sk + 31) / 32 * 32, 32, RR, s, 2);
-    pl.splitk = (int)((M + chunk - 1) / chunk);
-    pl.chunk = chunk;
+    wgrad_plan_tail(pl, s, M, RR, sk, 32, true, 2);
     return pl;
 }
 
@@ -1373,13 +1398,8 @@ static int conv2d_fwd_bf16_impl(const void *x, const void *w_bf16, const float *
     if (!x || !w_bf16 || !y || !rcf_aligned16(x) || !rcf_aligned16(w_bf16) || !rcf_aligned16(y)) return RCF_EINVAL;
     if (ydt == RCF_BF16 ? (s->y_pitch % 8) : (s->y_pitch % 4)) return RCF_EINVAL;
     ConvParams p{};
-    p.flags = s->flags;
     p.A = (const bf16_t *)x; p.Bw = (const bf16_t *)w_bf16; p.bias = bias; p.Y = y;
-    p.Ncol = s->Cout; p.K = s->R * s->S * s->Cin;
-    p.Ho = s->Ho; p.Wo = s->Wo; p.Hs = s->H; p.Ws = s->W; p.Cs = s->Cin; p.S = s->S;
-    if (int e = set_region(p, region, s->N, s->Ho, s->Wo)) return e;
-    p.up = s->stride; p.off = -s->pad; p.step = s->dil; p.div = 1;
-    p.a_pitch = s->x_pitch; p.a_img_stride = (long)s->H * s->W * s->x_pitch; p.y_pitch = s->y_pitch;
+    if (int e = conv_geometry(p, s, region, false)) return e;
     p.act = act; p.slope = slope; p.beta = beta;
     hipStream_t st = rcf_stream(stream);
     const bool stats = sums || fin;
@@ -1430,14 +1450,9 @@ extern "C" int rcf_conv2d_dgrad_bf16(const void *dy, const float *w, void *dx, c
         return RCF_EINVAL;
     }
     ConvParams p{};
-    p.flags = s->flags;
-    p.A = (const bf16_t *)dy; p.Bw = (const bf16_t *)wt; p.bias = nullptr; p.Y = dx;
-    p.Ncol = s->Cin; p.K = s->R * s->S * s->Cout;
-    p.Ho = s->H; p.Wo = s->W; p.Hs = s->Ho; p.Ws = s->Wo; p.Cs = s->Cout; p.S = s->S;
-    if (int e = set_region(p, region, s->N, s->H, s->W)) return e;
-    p.up = 1; p.off = s->pad; p.step = -s->dil; p.div = s->stride;
-    p.a_pitch = s->y_pitch; p.a_img_stride = (long)s->Ho * s->Wo * s->y_pitch; p.y_pitch = s->x_pitch;
-    p.act = 0; p.slope = 0.f; p.beta = beta;
+    p.A = (const bf16_t *)dy; p.Bw = (const bf16_t *)wt; p.Y = dx;
+    if (int e = conv_geometry(p, s, region, true)) return e;
+    p.beta = beta;
     return launch_conv<true>(p, true, rcf_stream(stream));
 }
 
@@ -1458,13 +1473,8 @@ extern "C" int rcf_conv2d_fwd_affine_bf16(const void *x, const void *w_bf16, con
     if (s->y_pitch % 8 || (residual && (!rcf_aligned16(residual) || res_pitch % 8 || res_pitch < s->Cout))) return RCF_EINVAL;
     if (s->stride != 1) return RCF_EINVAL;
     ConvParams p{};
-    p.flags = s->flags;
-    p.A = (const bf16_t *)x; p.Bw = (const bf16_t *)w_bf16; p.bias = nullptr; p.Y = y;
-    p.Ncol = s->Cout; p.K = s->R * s->S * s->Cin;
-    p.Ho = s->Ho; p.Wo = s->Wo; p.Hs = s->H; p.Ws = s->W; p.Cs = s->Cin; p.S = s->S;
-    if (int e = set_region(p, nullptr, s->N, s->Ho, s->Wo)) return e;
-    p.up = s->stride; p.off = -s->pad; p.step = s->dil; p.div = 1;
-    p.a_pitch = s->x_pitch; p.a_img_stride = (long)s->H * s->W * s->x_pitch; p.y_pitch = s->y_pitch;
+    p.A = (const bf16_t *)x; p.Bw = (const bf16_t *)w_bf16; p.Y = y;
+    if (int e = conv_geometry(p, s, nullptr, false)) return e;
     p.ep_scale = scale; p.ep_shift = shift; p.ep_side = (const bf16_t *)residual; p.ep_side_pitch = res_pitch; p.ep_relu = relu;
     p.ep_bits = relu ? (unsigned long long *)relu_bits : nullptr;
     return launch_conv<true>(p, false, rcf_stream(stream), 1);
@@ -1484,13 +1494,8 @@ extern "C" int rcf_conv2d_dgrad_masked_bf16(const void *dy, const void *w_t_bf16
     if (mask_src && (!rcf_aligned16(mask_src) || mask_pitch % 8 || mask_pitch < s->Cin)) return RCF_EINVAL;
     if (s->y_pitch % 8 || s->stride != 1) return RCF_EINVAL;
     ConvParams p{};
-    p.flags = s->flags;
-    p.A = (const bf16_t *)dy; p.Bw = (const bf16_t *)w_t_bf16; p.bias = nullptr; p.Y = dx;
-    p.Ncol = s->Cin; p.K = s->R * s->S * s->Cout;
-    p.Ho = s->H; p.Wo = s->W; p.Hs = s->Ho; p.Ws = s->Wo; p.Cs = s->Cout; p.S = s->S;
-    if (int e = set_region(p, nullptr, s->N, s->H, s->W)) return e;
-    p.up = 1; p.off = s->pad; p.step = -s->dil; p.div = s->stride;
-    p.a_pitch = s->y_pitch; p.a_img_stride = (long)s->Ho * s->Wo * s->y_pitch; p.y_pitch = s->x_pitch;
+    p.A = (const bf16_t *)dy; p.Bw = (const bf16_t *)w_t_bf16; p.Y = dx;
+    if (int e = conv_geometry(p, s, nullptr, true)) return e;
     p.beta = beta;
     p.ep_side = (const bf16_t *)mask_src; p.ep_side_pitch = mask_pitch;
     p.ep_bits = (unsigned long long *)mask_bits;
@@ -1507,9 +1512,7 @@ extern "C" int rcf_conv2d_dgrad_masked_bf16(const void *dy, const void *w_t_bf16
 
 extern "C" size_t rcf_conv2d_wgrad_bf16_workspace_bytes(const rcf_conv_shape *s, const rcf_conv_region *region) {
     if (check_shape(s) || !region_ok(region, s->Ho, s->Wo)) return 0;
-    const WgradPlan pl = plan_wgrad(s, region);
-    if (pl.splitk <= 1) return 0;
-    return (size_t)pl.splitk * s->Cout * s->R * s->S * s->Cin * sizeof(float);
+    return wgrad_workspace_bytes(plan_wgrad(s, region).splitk, s);
 }
 
 extern "C" int rcf_conv2d_wgrad_bf16(const void *x, const void *dy, float *dw, const rcf_conv_shape *s,
@@ -1519,45 +1522,39 @@ extern "C" int rcf_conv2d_wgrad_bf16(const void *x, const void *dy, float *dw, c
     if (!x || !dy || !dw || !rcf_aligned16(x) || !rcf_aligned16(dy) || !rcf_aligned16(dw)) return RCF_EINVAL;
     if (s->y_pitch % 8 || !region_ok(region, s->Ho, s->Wo)) return RCF_EINVAL;
     const WgradPlan pl = plan_wgrad(s, region);
-    const size_t need = rcf_conv2d_wgrad_bf16_workspace_bytes(s, region);
-    if (need > 0 && (!workspace || workspace_bytes < need || !rcf_aligned16(workspace))) return RCF_EWORKSPACE;
+    if (pl.splitk > 1 && (!workspace || workspace_bytes < wgrad_workspace_bytes(pl.splitk, s) || !rcf_aligned16(workspace))) return RCF_EWORKSPACE;
     hipStream_t st = rcf_stream(stream);
     WgradParams p{};
     p.X = (const bf16_t *)x; p.DY = (const bf16_t *)dy;
-    p.OUT = pl.splitk > 1 ? (float *)workspace : dw;
-    p.Cout = s->Cout; p.Cin = s->Cin; p.R = s->R; p.S = s->S;
-    p.H = s->H; p.W = s->W; p.Ho = s->Ho; p.Wo = s->Wo; p.stride = s->stride; p.pad = s->pad; p.dil = s->dil;
-    p.x_pitch = s->x_pitch; p.dy_pitch = s->y_pitch;
-    fill_region(p, region, s->N, s->Ho, s->Wo);
-    p.chunk = pl.chunk; p.itiles = pl.itiles; p.jtiles = pl.jtiles;
-    p.split_stride = (long)s->Cout * s->R * s->S * s->Cin; p.beta = beta;
+    fill_wgrad(p, pl, s, region, beta, dw, workspace);
     p.Ktot = s->R * s->S * s->Cin;
     p.sched = 1;
-    p.xcd_map = (s->flags & RCF_CONV_NO_WGRAD_XCD) ? 0 : 1;
     const dim3 grid((unsigned)(pl.itiles * pl.jtiles), 1u, (unsigned)pl.splitk);
-#define RCF_WG(MRv, NRv)                                                                              \
-    do {                                                                                              \
-        if (region) hipLaunchKernelGGL((wgrad_bf16_kernel<MRv, NRv, true>), grid, dim3(256), 0, st, p);  \
-        else hipLaunchKernelGGL((wgrad_bf16_kernel<MRv, NRv, false>), grid, dim3(256), 0, st, p);        \
-    } while (0)
-    const bool onetap = s->Cin % (64 * pl.nr) == 0;
-    p.cblocks = onetap && s->R * s->S > 1 && p.xcd_map ? s->Cin / (64 * pl.nr) : 0;
-#define RCF_WGD(NRv)                                                                                              \
-    do {                                                                                                          \
-        if (region && onetap) hipLaunchKernelGGL((wgrad_bf16_dma_kernel<NRv, true, true>), grid, dim3(256), 0, st, p);   \
-        else if (region) hipLaunchKernelGGL((wgrad_bf16_dma_kernel<NRv, true, false>), grid, dim3(256), 0, st, p);       \
-        else if (onetap) hipLaunchKernelGGL((wgrad_bf16_dma_kernel<NRv, false, true>), grid, dim3(256), 0, st, p);       \
-        else hipLaunchKernelGGL((wgrad_bf16_dma_kernel<NRv, false, false>), grid, dim3(256), 0, st, p);                  \
-    } while (0)
-    if (pl.mr == 2 && pl.nr == 4) RCF_WGD(4);
-    else if (pl.mr == 2 && pl.nr == 2) RCF_WGD(2);
-    else if (pl.mr == 2) RCF_WG(2, 1);
-    else if (pl.nr == 4) RCF_WG(1, 4);
-    else if (pl.nr == 2) RCF_WG(1, 2);
-    else RCF_WG(1, 1);
-#undef RCF_WG
-#undef RCF_WGD
+    const bool reg = region != nullptr;
+#define RCF_GO(...) hipLaunchKernelGGL((__VA_ARGS__), grid, dim3(256), 0, st, p)
+    switch (pl.kernel) {
+        case WG_BF16_DMA:                        // <NR, REGION, ONETAP>
+            if (pl.nr == 4) RCF_GO_BB(reg, pl.onetap, wgrad_bf16_dma_kernel, 4); else RCF_GO_BB(reg, pl.onetap, wgrad_bf16_dma_kernel, 2);
+            break;
+        case WG_BF16:                            // <MR, NR, REGION>
+            if (pl.mr == 2) RCF_GO_B(reg, wgrad_bf16_kernel, 2, 1);
+            else if (pl.nr == 4) RCF_GO_B(reg, wgrad_bf16_kernel, 1, 4);
+            else if (pl.nr == 2) RCF_GO_B(reg, wgrad_bf16_kernel, 1, 2);
+            else RCF_GO_B(reg, wgrad_bf16_kernel, 1, 1);
+    }
+#undef RCF_GO
     RCF_LAUNCH_CHECK();
     if (pl.splitk > 1) return rcf_splitk_reduce((const float *)workspace, dw, p.split_stride, p.split_stride, pl.splitk, beta, stream);
+    return 0;
+}
+
+// rcf_common.h: rcf_conv_plan_of for 16-bit tensors.  Forward and data gradient have one kernel, conv_bf16_kernel, whose tile
+// follows the output width (launch_conv); the forward is checked as for fp32 output, the loosest form its entry point takes.
+int rcf_conv_plan_bf16(const rcf_conv_shape *s, const rcf_conv_region *region, int direction, rcf_conv_plan *out) {
+    if (int e = check_shape(s, direction == 0 ? 4 : 8)) return e;
+    if ((direction && s->y_pitch % 8) || !region_ok(region, direction == 1 ? s->H : s->Ho, direction == 1 ? s->W : s->Wo)) return RCF_EINVAL;
+    const WgradPlan pl = plan_wgrad(s, region);
+    *out = direction == 2 ? rcf_conv_plan{pl.kernel, 64 * pl.mr, 64 * pl.nr, pl.splitk}
+                          : rcf_conv_plan{RCF_KERNEL_BF16, 128, conv_bn_of(direction == 1 ? s->Cin : s->Cout), 1};
     return 0;
 }

@@ -2089,75 +2089,6 @@ inline bool use_x3(unsigned flags) { return fp32_mfma_variant(flags) < 0; }
 // the RCF_CONV_FP32_MFMA test variants keep the kernels they are there to exercise
 inline bool thin_path(const rcf_conv_shape *s) { return use_x3(s->flags) && !(s->flags & RCF_CONV_NO_THIN) && rcf_thin_ok(s); }
 
-template <int BMODE, int BKT, bool RM>
-int launch_igemm_v(IgemmParams &p, hipStream_t st) {
-    p.cs_magic = magic_of(p.Cs);
-    p.s_magic = magic_of(p.S);
-    if ((long)p.K * p.Cs >= (1L << 32)) return RCF_EINVAL;
-    const bool strided = BMODE == 1 && p.div > 1;
-    // tile: 128x64 for narrow outputs, 128x128 by default, 128x256 (8 accumulator tiles per wave: twice the
-    // MFMA work per barrier) when the output is wide and there are enough row tiles to fill the chip
-    const bool wide = p.Ncol > 64;
-    const int BM = 128, BN = wide ? 128 : 64;
-    p.mtiles = rcf_cdiv(p.M, BM);
-    p.mtiles8 = rcf_cdiv(p.mtiles, 8);
-    p.ntiles = rcf_cdiv(p.Ncol, BN);
-    const int groups = rcf_cdiv(p.mtiles, 8);
-    const dim3 grid((unsigned)(groups * 8 * p.ntiles));
-    if (strided) {
-        if (wide) hipLaunchKernelGGL((igemm_conv_kernel<2, 2, BMODE, BKT, RM, BMODE == 1>), grid, dim3(256), 0, st, p);
-        else hipLaunchKernelGGL((igemm_conv_kernel<2, 1, BMODE, BKT, RM, BMODE == 1>), grid, dim3(256), 0, st, p);
-    } else {
-        if (wide) hipLaunchKernelGGL((igemm_conv_kernel<2, 2, BMODE, BKT, RM, false>), grid, dim3(256), 0, st, p);
-        else hipLaunchKernelGGL((igemm_conv_kernel<2, 1, BMODE, BKT, RM, false>), grid, dim3(256), 0, st, p);
-    }
-    RCF_LAUNCH_CHECK();
-    return 0;
-}
-
-// split-bf16 launch (B always k-contiguous)
-template <int MR, int NR, int WM, int WN, int NP, bool PRE = false>
-void launch_x3_cfg_np(IgemmParams &p, bool strided, hipStream_t st, int batches) {
-    constexpr int BM = 32 * MR * WM, BN = 32 * NR * WN;
-    p.mtiles = rcf_cdiv(p.M, BM);
-    p.mtiles8 = rcf_cdiv(p.mtiles, 8);
-    p.ntiles = rcf_cdiv(p.Ncol, BN);
-    p.colmap = batches == 1 && p.Ncol % BN == 0 &&
-               rcf_colmap_pays(!(p.flags & RCF_CONV_NO_COLMAP), (long)p.M * p.Cs * 4, (long)p.K * p.Ncol * 4, p.mtiles, p.ntiles);
-    const dim3 grid((unsigned)(rcf_cdiv(p.mtiles, 8) * 8 * p.ntiles), (unsigned)batches);
-    if (p.tapskip) {                             // the tap-list instances (launch_igemm_x3: never strided or batched)
-        if constexpr (NP == 2 && PRE) {
-            if (p.stats && p.step < 0) {
-                hipLaunchKernelGGL((igemm_conv_x3_kernel<MR, NR, WM, WN, false, true, NP, PRE, true, true, true>), grid, dim3(64 * WM * WN), 0, st, p);
-                return;
-            }
-        }
-        if (p.step < 0) hipLaunchKernelGGL((igemm_conv_x3_kernel<MR, NR, WM, WN, false, true, NP, PRE, true, false, true>), grid, dim3(64 * WM * WN), 0, st, p);
-        else hipLaunchKernelGGL((igemm_conv_x3_kernel<MR, NR, WM, WN, false, false, NP, PRE, true, false, true>), grid, dim3(64 * WM * WN), 0, st, p);
-        return;
-    }
-    if constexpr (NP == 2 && PRE) {              // data gradient + the batch-norm backward sums (rcf_conv2d_dgrad_bnsums_f32)
-        if (p.stats && p.step < 0) {
-            if (strided) hipLaunchKernelGGL((igemm_conv_x3_kernel<MR, NR, WM, WN, true, true, NP, PRE, true, true>), grid, dim3(64 * WM * WN), 0, st, p);
-            else hipLaunchKernelGGL((igemm_conv_x3_kernel<MR, NR, WM, WN, false, true, NP, PRE, true, true>), grid, dim3(64 * WM * WN), 0, st, p);
-            return;
-        }
-    }
-    if (strided) hipLaunchKernelGGL((igemm_conv_x3_kernel<MR, NR, WM, WN, true, true, NP, PRE>), grid, dim3(64 * WM * WN), 0, st, p);
-    else if (p.step < 0) hipLaunchKernelGGL((igemm_conv_x3_kernel<MR, NR, WM, WN, false, true, NP, PRE>), grid, dim3(64 * WM * WN), 0, st, p);
-    else hipLaunchKernelGGL((igemm_conv_x3_kernel<MR, NR, WM, WN, false, false, NP, PRE, true>), grid, dim3(64 * WM * WN), 0, st, p);
-}
-
-template <int MR, int NR, int WM, int WN>
-void launch_x3_cfg(IgemmParams &p, bool strided, hipStream_t st, int batches = 1) {
-    if (p.amax_a && p.amax_b) {
-        if (p.b_pairs) launch_x3_cfg_np<MR, NR, WM, WN, 2, true>(p, strided, st, batches);
-        else launch_x3_cfg_np<MR, NR, WM, WN, 2>(p, strided, st, batches);
-    } else {
-        launch_x3_cfg_np<MR, NR, WM, WN, 3>(p, strided, st, batches);
-    }
-}
-
 // conv_h2p_kernel (igemm_h2p.inc): which launches take it.  Built-in rule: K >= H2P_MIN_K, i.e. the 3x3 layers.  Below (1x1
 // convs, K <= 2048) the epilogue (256 KB of output per tile) is a large part of a tile's time and the kernel's single workgroup
 // per CU has nothing to overlap it with: measured 0.90-1.0x of the 128x256 kernel there, 1.04-1.17x on the 3x3 layers.
@@ -2205,128 +2136,205 @@ bool h2p_eligible(const IgemmParams &p, int batches) {
                                                (long)rcf_cdiv(p.M, 128) * (p.Ncol / 256) <= 2048);
 }
 
-int launch_h2p(IgemmParams &p, hipStream_t st) {
-    const long bytes = (long)(p.K / 16) * p.Ncol * 64;
-    const long per_tile_imgs = 256 / (long)p.rr + 2;
-    if (bytes >= (1L << 31) || per_tile_imgs * p.a_img_stride * 4 >= (1L << 31)) return RCF_EINVAL;
-    p.b_bytes = (int)bytes;
-    p.ntiles = p.Ncol / 256;
-    p.h2p_gn = h2p_gn(p.M, p.ntiles);
-    p.mtiles8 = h2p_stat_rows(p.M, p.h2p_gn);
-    p.mtiles = (H2P_G / p.h2p_gn) * p.mtiles8;                          // rows of partial statistics (rcf_conv2d_fwd_bnstats_f32)
-    if (p.step < 0) hipLaunchKernelGGL(conv_h2p_kernel<true>, dim3(H2P_G), dim3(256), 0, st, p);
-    else hipLaunchKernelGGL(conv_h2p_kernel<false>, dim3(H2P_G), dim3(256), 0, st, p);
-    RCF_LAUNCH_CHECK();
-    return 0;
+// ---- Plan, then launch.  A forward, data-gradient or GEMM launch is decided ONCE, by plan_conv, into a ConvPlan; launch_conv
+// only selects the instantiation the plan names.  Every refusal is the planner's, so nothing runs before a launch is refused, and
+// "which kernel would this call take" (rcf_conv_plan_of) is the planner's answer, not a dry run of the launch.
+struct ConvPlan {
+    int kernel;                   // include/rcf_hip.h RCF_KERNEL_MFMA / _TILE / _H2P / _H2D
+    int mr, nr;                   // tile: 64 mr rows x 64 nr columns (conv_h2p_kernel: 32-row blocks x 256 columns)
+    int variant;                  // RCF_KERNEL_MFMA: bit 0 = K-step 32, bit 1 = row-major LDS tiles (RCF_CONV_FP32_MFMA)
+    bool dgrad, strided;          // source walk: taps mirrored (step < 0); only every div-th source coordinate exists
+    int np;                       // partial products: 2 (fp16 pairs: both operand ranges given) or 3 (bf16 triples)
+    bool pre, lean;               // the weights arrive split (b_pairs); data gradient with the lean epilogue (sums / masked addend)
+    unsigned gx, gy;              // grid
+    int tapskip, rorder, mtiles, mtiles8, ntiles, colmap, b_bytes, h2p_gn, kch, rsch;       // for IgemmParams (launch_conv)
+    unsigned cs_magic, s_magic, kch_magic, rsch_magic;
+};
+
+// row / column tiles of a BM x BN tile, the XCD column map (rcf_common.h rcf_colmap_pays) and the grid of the tile kernels
+void plan_tiles(ConvPlan &pl, const IgemmParams &p, int batches) {
+    const int BN = 64 * pl.nr;
+    pl.mtiles = rcf_cdiv(p.M, 64 * pl.mr);
+    pl.mtiles8 = rcf_cdiv(pl.mtiles, 8);
+    pl.ntiles = rcf_cdiv(p.Ncol, BN);
+    if (pl.kernel != RCF_KERNEL_MFMA)
+        pl.colmap = batches == 1 && p.Ncol % BN == 0 &&
+                    rcf_colmap_pays(!(p.flags & RCF_CONV_NO_COLMAP), (long)p.M * p.Cs * 4, (long)p.K * p.Ncol * 4, pl.mtiles, pl.ntiles);
+    pl.gx = (unsigned)(pl.mtiles8 * 8 * pl.ntiles);
+    pl.gy = (unsigned)batches;
 }
 
-// conv_h2d_kernel (igemm_h2d.inc): the activation operand arrives as fp16 pair planes -- the only kernel that reads them
-int launch_h2d(IgemmParams &p, hipStream_t st, int batches, int *kernel_only) {
-    if (!p.b_pairs2 || !p.amax_a || !p.amax_b || batches != 1 || p.batch1 > 0) return RCF_EINVAL;
-    if (p.K % 16 || p.Cs % 16 || p.a_pitch != p.Cs || p.Ncol % 4) return RCF_EINVAL;
-    const long bytes = (long)(p.K / 16) * p.Ncol * 64;
-    const long per_tile_imgs = 256 / (long)p.rr + 2;
-    if (bytes >= (1L << 31) || per_tile_imgs * p.a_img_stride * 4 >= (1L << 31)) return RCF_EINVAL;
-    if (kernel_only) { *kernel_only = 3; return 0; }
-    p.b_bytes = (int)bytes;
-    const int BN = p.Ncol > 128 ? 256 : (p.Ncol > 64 ? 128 : 64);
-    p.mtiles = rcf_cdiv(p.M, 128);
-    p.mtiles8 = rcf_cdiv(p.mtiles, 8);
-    p.ntiles = rcf_cdiv(p.Ncol, BN);
-    p.colmap = p.Ncol % BN == 0 &&
-               rcf_colmap_pays(!(p.flags & RCF_CONV_NO_COLMAP), (long)p.M * p.Cs * 4, (long)p.K * p.Ncol * 4, p.mtiles, p.ntiles);
-    const dim3 grid((unsigned)(p.mtiles8 * 8 * p.ntiles));
-#define RCF_H2D(NRv)                                                                                            \
-    do {                                                                                                        \
-        if (p.stats && p.step < 0 && p.div > 1) hipLaunchKernelGGL((conv_h2d_kernel<NRv, true, true, true>), grid, dim3(256), 0, st, p); \
-        else if (p.stats && p.step < 0) hipLaunchKernelGGL((conv_h2d_kernel<NRv, false, true, true>), grid, dim3(256), 0, st, p);        \
-        else if (p.div > 1) hipLaunchKernelGGL((conv_h2d_kernel<NRv, true, true>), grid, dim3(256), 0, st, p);  \
-        else if (p.step < 0) hipLaunchKernelGGL((conv_h2d_kernel<NRv, false, true>), grid, dim3(256), 0, st, p); \
-        else hipLaunchKernelGGL((conv_h2d_kernel<NRv, false, false>), grid, dim3(256), 0, st, p);               \
-    } while (0)
-    if (BN == 256) RCF_H2D(4);
-    else if (BN == 128) RCF_H2D(2);
-    else RCF_H2D(1);
-#undef RCF_H2D
-    RCF_LAUNCH_CHECK();
-    return 0;
-}
-
-// `kernel_only`: do not launch, report which kernel the call would take (rcf_conv_kernel_of: 1 the 128 x 256 family, 2 conv_h2p_kernel,
-// 3 conv_h2d_kernel)
-int launch_igemm_x3(IgemmParams &p, hipStream_t st, int batches = 1, int *kernel_only = nullptr) {
-    p.cs_magic = magic_of(p.Cs);
-    {
-        const int taps = p.K / p.Cs, kch = rcf_kchunk(korder_chunked(p.flags), taps, p.Cs, RCF_KCHUNK_F32);
-        p.kch = kch ? kch : p.Cs;
-        p.rsch = taps * p.kch;
-        p.kch_magic = magic_of(p.kch);
-        p.rsch_magic = magic_of(p.rsch);
-        if ((long)(p.K + 16) * p.rsch >= (1L << 32)) return RCF_EINVAL;
-    }
-    p.s_magic = magic_of(p.S);
+// Fills `pl` from the launch parameters (scalars, and which operand pointers are null: nothing is read through them) and returns
+// 0 / RCF_EINVAL.  batches: products per launch (rcf_gemm_nt_batched_f32); presplit: the weights are fp16 pairs by launch time
+// whenever both operand ranges are given (prepared by the caller, or split by the data gradient's own pre-pass).
+int plan_conv(const IgemmParams &p, int batches, bool presplit, ConvPlan &pl) {
+    pl = ConvPlan{};
+    pl.dgrad = p.step < 0;
+    pl.strided = p.div > 1;
+    pl.cs_magic = magic_of(p.Cs);
+    pl.s_magic = magic_of(p.S);
     if ((long)p.K * p.Cs >= (1L << 32)) return RCF_EINVAL;
-    const bool tap_skip = !(p.flags & RCF_CONV_NO_TAP_SKIP);
-    p.rorder = RCF_REGION_ROWMAJOR;             // conv_h2d_kernel / conv_h2p_kernel: no tap lists, the order they always had
-    if (p.a_split) return p.src_band > 0 ? RCF_EINVAL : launch_h2d(p, st, batches, kernel_only);
-    if (kernel_only) {
-        *kernel_only = h2p_eligible(p, batches) ? 2 : 1;
+    if (!use_x3(p.flags)) {
+        // fp32-MFMA test path.  Tile: 128x64 for narrow outputs, 128x128 otherwise
+        pl.kernel = RCF_KERNEL_MFMA;
+        pl.variant = fp32_mfma_variant(p.flags) & 3;
+        pl.mr = 2; pl.nr = p.Ncol > 64 ? 2 : 1;
+        plan_tiles(pl, p, 1);
         return 0;
     }
-    if (h2p_eligible(p, batches)) return launch_h2p(p, st);
-    // 32-bit descriptor offsets: the images one row tile can touch must lie within 2 GiB of the first one
-    const long per_tile_imgs = 256 / (long)p.rr + 2;
-    if (per_tile_imgs * p.a_img_stride * 4 >= (1L << 31) || (long)p.Ncol * p.ldb * 4 >= (1L << 31)) return RCF_EINVAL;
-    p.b_bytes = (int)((long)p.Ncol * p.ldb * 4);
-    if (p.b_pairs && p.amax_a && p.amax_b) {     // K-step-major pairs: K padded to whole steps
-        const long bytes = (long)rcf_cdiv(p.K, 16) * p.Ncol * 64;
-        if (bytes >= (1L << 31)) return RCF_EINVAL;
-        p.b_bytes = (int)bytes;
+    const int taps = p.K / p.Cs, kch = rcf_kchunk(korder_chunked(p.flags), taps, p.Cs, RCF_KCHUNK_F32);
+    pl.kch = kch ? kch : p.Cs;
+    pl.rsch = taps * pl.kch;
+    pl.kch_magic = magic_of(pl.kch);
+    pl.rsch_magic = magic_of(pl.rsch);
+    if ((long)(p.K + 16) * pl.rsch >= (1L << 32)) return RCF_EINVAL;
+    pl.np = (p.amax_a && p.amax_b) ? 2 : 3;
+    pl.pre = pl.np == 2 && presplit;
+    pl.rorder = RCF_REGION_ROWMAJOR;             // conv_h2d_kernel / conv_h2p_kernel: no tap lists, the order they always had
+    // 32-bit descriptor offsets: the images one row tile can touch must lie within 2 GiB of the first one, and so must the weights
+    const bool far = (256 / (long)p.rr + 2) * p.a_img_stride * 4 >= (1L << 31);
+    const long dma_bytes = (long)(p.K / 16) * p.Ncol * 64;            // the plane-separated K-step blocks (b_pairs2)
+    if (p.a_split) {
+        // conv_h2d_kernel (igemm_h2d.inc): the activation operand arrives as fp16 pair planes -- the only kernel that reads them
+        if (p.src_band > 0 || !p.b_pairs2 || !p.amax_a || !p.amax_b || batches != 1 || p.batch1 > 0) return RCF_EINVAL;
+        if (p.K % 16 || p.Cs % 16 || p.a_pitch != p.Cs || p.Ncol % 4) return RCF_EINVAL;
+        if (dma_bytes >= (1L << 31) || far) return RCF_EINVAL;
+        pl.kernel = RCF_KERNEL_H2D;
+        pl.b_bytes = (int)dma_bytes;
+        pl.mr = 2; pl.nr = p.Ncol > 128 ? 4 : (p.Ncol > 64 ? 2 : 1);
+        pl.lean = p.stats && pl.dgrad;
+        plan_tiles(pl, p, 1);
+        return 0;
     }
-    const bool strided = p.div > 1;
-    {
-        // the tap-list K loop of igemm_conv_x3_kernel: several taps (at most 32: one mask word), whole K-steps inside one tap, unit
-        // stride, one product.  A source frame needs that loop's loads even where the list holds every tap (bit 1).
-        // Frames only: on a whole tensor the edge lines are 3 % of the steps, and the list's step arithmetic cost the 3x3 forward
-        // launches of the step 3 - 8 % (profiles/tap_skip_kernel_stats.txt) -- those keep the plain loop.
-        const int taps = p.K / p.Cs;
-        const bool can = !strided && batches == 1 && p.batch1 == 0 && taps > 1 && taps <= 32 && p.kch % 16 == 0 &&
-                         (p.rband > 0 || p.src_band > 0);
-        if (p.src_band > 0 && (strided || batches != 1 || p.batch1 != 0 || taps > 32)) return RCF_EINVAL;
-        p.tapskip = (can && tap_skip) ? 1 : (p.src_band > 0 ? 3 : 0);
-        // ... and frames by depth (region_order.h), so that the rows of a tile share the taps that read nothing; fused
-        // statistics are sums over a tile's pixels and keep the order they were checked under
-        if (p.tapskip == 1 && !p.stats) p.rorder = RCF_REGION_BYDEPTH;
+    if (h2p_eligible(p, batches)) {
+        if (dma_bytes >= (1L << 31) || far) return RCF_EINVAL;
+        pl.kernel = RCF_KERNEL_H2P;
+        pl.b_bytes = (int)dma_bytes;
+        pl.nr = 4;
+        pl.ntiles = p.Ncol / 256;
+        pl.h2p_gn = h2p_gn(p.M, pl.ntiles);
+        pl.mtiles8 = h2p_stat_rows(p.M, pl.h2p_gn);
+        pl.mtiles = (H2P_G / pl.h2p_gn) * pl.mtiles8;                      // rows of partial statistics (rcf_conv2d_fwd_bnstats_f32)
+        pl.gx = H2P_G; pl.gy = 1;
+        return 0;
     }
-    if (p.Ncol <= 64 && (long)rcf_cdiv(p.M, 128) * batches < 512) launch_x3_cfg<1, 1, 2, 2>(p, strided, st, batches);   // few rows: 64x64 tiles fill more CUs
-    else if (p.Ncol <= 64) launch_x3_cfg<2, 1, 2, 2>(p, strided, st, batches);
-    else if (p.Ncol > 128) launch_x3_cfg<2, 4, 2, 2>(p, strided, st, batches);
-    else launch_x3_cfg<2, 2, 2, 2>(p, strided, st, batches);
+    pl.kernel = RCF_KERNEL_TILE;
+    if (far || (long)p.Ncol * p.ldb * 4 >= (1L << 31)) return RCF_EINVAL;
+    pl.b_bytes = (int)((long)p.Ncol * p.ldb * 4);
+    const long pair_bytes = (long)rcf_cdiv(p.K, 16) * p.Ncol * 64;      // K-step-major pairs: K padded to whole steps
+    if (pl.pre && pair_bytes >= (1L << 31)) return RCF_EINVAL;
+    if (pl.pre) pl.b_bytes = (int)pair_bytes;
+    // the tap-list K loop of igemm_conv_x3_kernel: several taps (at most 32: one mask word), whole K-steps inside one tap, unit
+    // stride, one product.  A source frame needs that loop's loads even where the list holds every tap (bit 1).
+    // Frames only: on a whole tensor the edge lines are 3 % of the steps, and the list's step arithmetic cost the 3x3 forward
+    // launches of the step 3 - 8 % (profiles/tap_skip_kernel_stats.txt) -- those keep the plain loop.
+    const bool one = !pl.strided && batches == 1 && p.batch1 == 0;
+    const bool can = one && taps > 1 && taps <= 32 && pl.kch % 16 == 0 && (p.rband > 0 || p.src_band > 0);
+    if (p.src_band > 0 && (!one || taps > 32)) return RCF_EINVAL;
+    pl.tapskip = (can && !(p.flags & RCF_CONV_NO_TAP_SKIP)) ? 1 : (p.src_band > 0 ? 3 : 0);
+    // ... and frames by depth (region_order.h), so that the rows of a tile share the taps that read nothing; fused
+    // statistics are sums over a tile's pixels and keep the order they were checked under
+    if (pl.tapskip == 1 && !p.stats) pl.rorder = RCF_REGION_BYDEPTH;
+    pl.lean = pl.pre && p.stats && pl.dgrad;
+    pl.mr = 2;
+    if (p.Ncol <= 64 && (long)rcf_cdiv(p.M, 128) * batches < 512) { pl.mr = 1; pl.nr = 1; }     // few rows: 64x64 tiles fill more CUs
+    else pl.nr = p.Ncol <= 64 ? 1 : (p.Ncol > 128 ? 4 : 2);
+    plan_tiles(pl, p, batches);
+    return 0;
+}
+
+#define RCF_GO(...) hipLaunchKernelGGL((__VA_ARGS__), grid, block, 0, st, p)
+
+template <int BKT, bool RM>
+void launch_mfma(const IgemmParams &p, const ConvPlan &pl, dim3 grid, dim3 block, hipStream_t st) {
+    const bool wide = pl.nr == 2;
+    if (pl.dgrad && wide) RCF_GO_B(pl.strided, igemm_conv_kernel, 2, 2, 1, BKT, RM);       // <MR, NR, BMODE, BKT, RM, STRIDED>
+    else if (pl.dgrad) RCF_GO_B(pl.strided, igemm_conv_kernel, 2, 1, 1, BKT, RM);
+    else if (wide) RCF_GO(igemm_conv_kernel<2, 2, 0, BKT, RM, false>);
+    else RCF_GO(igemm_conv_kernel<2, 1, 0, BKT, RM, false>);
+}
+
+// igemm_conv_x3_kernel<MR, NR, 2, 2, STRIDED, DGRAD, NP, PRE, TR, BST (lean epilogue), TAPS (tap-list loop)>
+template <int MR, int NR, int NP, bool PRE>
+void launch_x3(const IgemmParams &p, const ConvPlan &pl, dim3 grid, dim3 block, hipStream_t st) {
+    if constexpr (NP == 2 && PRE) {              // data gradient + the batch-norm backward sums / the masked addend
+        if (pl.lean) {
+            if (pl.tapskip) RCF_GO(igemm_conv_x3_kernel<MR, NR, 2, 2, false, true, NP, PRE, true, true, true>);
+            else if (pl.strided) RCF_GO(igemm_conv_x3_kernel<MR, NR, 2, 2, true, true, NP, PRE, true, true>);
+            else RCF_GO(igemm_conv_x3_kernel<MR, NR, 2, 2, false, true, NP, PRE, true, true>);
+            return;
+        }
+    }
+    if (pl.tapskip) {                            // the tap-list instances (plan_conv: never strided or batched)
+        if (pl.dgrad) RCF_GO(igemm_conv_x3_kernel<MR, NR, 2, 2, false, true, NP, PRE, true, false, true>);
+        else RCF_GO(igemm_conv_x3_kernel<MR, NR, 2, 2, false, false, NP, PRE, true, false, true>);
+    } else if (pl.strided) RCF_GO(igemm_conv_x3_kernel<MR, NR, 2, 2, true, true, NP, PRE>);
+    else if (pl.dgrad) RCF_GO(igemm_conv_x3_kernel<MR, NR, 2, 2, false, true, NP, PRE>);
+    else RCF_GO(igemm_conv_x3_kernel<MR, NR, 2, 2, false, false, NP, PRE, true>);
+}
+
+// conv_h2d_kernel<NR, STRIDED, DGRAD, BST (lean epilogue)>
+template <int NR>
+void launch_h2d(const IgemmParams &p, const ConvPlan &pl, dim3 grid, dim3 block, hipStream_t st) {
+    if (pl.lean && pl.strided) RCF_GO(conv_h2d_kernel<NR, true, true, true>);
+    else if (pl.lean) RCF_GO(conv_h2d_kernel<NR, false, true, true>);
+    else if (pl.strided) RCF_GO(conv_h2d_kernel<NR, true, true>);
+    else if (pl.dgrad) RCF_GO(conv_h2d_kernel<NR, false, true>);
+    else RCF_GO(conv_h2d_kernel<NR, false, false>);
+}
+
+// launches what the plan names: copies the plan's integers into the kernel parameters, then only selects the instantiation
+int launch_conv(IgemmParams &p, const ConvPlan &pl, hipStream_t st) {
+    p.tapskip = pl.tapskip; p.rorder = pl.rorder; p.mtiles = pl.mtiles; p.mtiles8 = pl.mtiles8; p.ntiles = pl.ntiles;
+    p.colmap = pl.colmap; p.b_bytes = pl.b_bytes; p.h2p_gn = pl.h2p_gn; p.kch = pl.kch; p.rsch = pl.rsch;
+    p.cs_magic = pl.cs_magic; p.s_magic = pl.s_magic; p.kch_magic = pl.kch_magic; p.rsch_magic = pl.rsch_magic;
+    const dim3 grid(pl.gx, pl.gy), block(256);
+    switch (pl.kernel) {
+        case RCF_KERNEL_MFMA:
+            if (pl.variant == 1) launch_mfma<32, false>(p, pl, grid, block, st);
+            else if (pl.variant == 2) launch_mfma<16, true>(p, pl, grid, block, st);
+            else if (pl.variant == 3) launch_mfma<32, true>(p, pl, grid, block, st);
+            else launch_mfma<16, false>(p, pl, grid, block, st);
+            break;
+        case RCF_KERNEL_H2P:
+            if (pl.dgrad) RCF_GO(conv_h2p_kernel<true>); else RCF_GO(conv_h2p_kernel<false>);
+            break;
+        case RCF_KERNEL_H2D:
+            if (pl.nr == 4) launch_h2d<4>(p, pl, grid, block, st);
+            else if (pl.nr == 2) launch_h2d<2>(p, pl, grid, block, st);
+            else launch_h2d<1>(p, pl, grid, block, st);
+            break;
+        default:
+#define RCF_X3(MR, NR) (pl.np == 3 ? launch_x3<MR, NR, 3, false> : pl.pre ? launch_x3<MR, NR, 2, true> : launch_x3<MR, NR, 2, false>)(p, pl, grid, block, st)
+            if (pl.mr == 1) RCF_X3(1, 1);
+            else if (pl.nr == 1) RCF_X3(2, 1);
+            else if (pl.nr == 4) RCF_X3(2, 4);
+            else RCF_X3(2, 2);
+#undef RCF_X3
+    }
     RCF_LAUNCH_CHECK();
     return 0;
 }
 
-template <int BMODE>
-int launch_igemm(IgemmParams &p, hipStream_t st) {
-    const int v = fp32_mfma_variant(p.flags) < 0 ? 0 : fp32_mfma_variant(p.flags);
-    switch (v & 3) {
-        case 1: return launch_igemm_v<BMODE, 32, false>(p, st);
-        case 2: return launch_igemm_v<BMODE, 16, true>(p, st);
-        case 3: return launch_igemm_v<BMODE, 32, true>(p, st);
-        default: return launch_igemm_v<BMODE, 16, false>(p, st);
-    }
-}
-
+enum WgradKernel { WG_MFMA = RCF_KERNEL_WGRAD_MFMA, WG_X3 = RCF_KERNEL_WGRAD_X3, WG_X3_WIDE = RCF_KERNEL_WGRAD_X3_WIDE,
+                   WG_H2T = RCF_KERNEL_WGRAD_H2T, WG_H2D = RCF_KERNEL_WGRAD_H2D };
 struct WgradPlan {
+    WgradKernel kernel;
     int mr, nr, itiles, jtiles, splitk;
     long chunk;
-    bool cols;      // igemm_wgrad_h2t_kernel: the taps are GEMM columns (grid.y = 1)
+    bool cols;      // the (tap, channel) pairs are GEMM columns (grid.y = 1): igemm_wgrad_h2t_kernel, igemm_wgrad_h2d_kernel
+    bool h2;        // fp16 pairs (both operand ranges given), not bf16 triples
+    bool onetap;    // conv_host.h wgrad_plan_tail
+    int cblocks;
 };
-WgradPlan plan_wgrad(const rcf_conv_shape *s, const rcf_conv_region *reg = nullptr) {
-    WgradPlan pl;
+// Tiles, split factor and kernel of a weight gradient.  Returns 0, or RCF_EINVAL for a launch that has no kernel -- after filling the
+// tile and split fields all the same: the workspace queries size the split-K buffer for every shape they are asked about.
+int plan_wgrad(const rcf_conv_shape *s, const rcf_conv_region *reg, WgradPlan &pl) {
+    pl = WgradPlan{};
     const bool x3 = use_x3(s->flags);
     const bool smallc = s->Cin == 4;
     const int ncols = smallc ? s->R * s->S * 4 : s->Cin;
+    pl.h2 = s->amax_dy && s->amax_x;
     pl.mr = s->Cout > 64 ? 2 : 1;
     pl.nr = ncols > 64 ? 2 : 1;
     // 128 x 256 tile (igemm_wgrad_x3_wide_kernel): whole tensors, wide enough operands
@@ -2337,7 +2345,7 @@ WgradPlan plan_wgrad(const rcf_conv_shape *s, const rcf_conv_region *reg = nullp
     // narrow layers are bound by memory, not by the half-empty tiles (1x1 64->256 and 256->64 at 120x214: 0.19 -> 0.12 ms
     // against the 64-wide kernels).
     const int ktot = s->R * s->S * s->Cin;
-    pl.cols = s->amax_dy && s->amax_x && x3 && !smallc && s->Cin % 64 == 0 && s->Cout >= 64 && !(reg && ktot < 256);
+    pl.cols = pl.h2 && x3 && !smallc && s->Cin % 64 == 0 && s->Cout >= 64 && !(reg && ktot < 256);
     if (pl.cols) {
         pl.mr = 2;
         pl.nr = ktot >= 256 ? 4 : 2;
@@ -2362,12 +2370,26 @@ WgradPlan plan_wgrad(const rcf_conv_shape *s, const rcf_conv_region *reg = nullp
         const double px_us = 0.075 * fmax((double)(pl.mr * pl.nr) / 8.0, 0.35);
         sk = splitk_search(tiles, M, slots, maxsk < 256 ? maxsk : 256, px_us, (double)s->Cout * s->R * s->S * s->Cin * 4.0);
     }
-    long chunk = ((M + sk - 1) / sk + BK - 1) / BK * BK;
-    if (x3 && !smallc) chunk = splitk_chunk_fit(chunk, BK, RR, s, 4);
-    sk = (M + chunk - 1) / chunk;
-    pl.splitk = (int)sk;
-    pl.chunk = chunk;
-    return pl;
+    wgrad_plan_tail(pl, s, M, RR, sk, BK, x3 && !smallc, 4);
+    // The kernel, and what has none.  Narrow tiles: the fp32-MFMA kernel is as fast as the bf16 triples; with operand ranges they
+    // take the fp16 pairs like every other conv of the step (same-box A/B: no difference in step time either way)
+    const unsigned planes = RCF_CONV_X_PLANES | RCF_CONV_DY_PLANES;
+    const bool split = x3 && !smallc && ((pl.mr == 2 && pl.nr >= 2) || reg || pl.h2);
+    pl.kernel = (s->flags & planes) ? WG_H2D : !split ? WG_MFMA : pl.cols ? WG_H2T : (pl.nr == 4 ? WG_X3_WIDE : WG_X3);
+    if (reg && (smallc || !x3)) return RCF_EINVAL;       // sub-rectangles exist on the split-bf16 / fp16-pair kernels only
+    // both operands as fp16 pair planes (igemm_h2dw.inc); one of them alone has no kernel
+    if (pl.kernel == WG_H2D && ((s->flags & planes) != planes || !pl.cols || pl.mr != 2 || s->Cout % 8 || s->x_pitch != s->Cin || s->y_pitch != s->Cout))
+        return RCF_EINVAL;
+    // 32-bit descriptor offsets: the images one pixel chunk touches
+    if (pl.kernel != WG_MFMA && (long)(pl.chunk / RR + 2) * s->H * s->W * s->x_pitch * 4 >= (1L << 31)) return RCF_EINVAL;
+    return 0;
+}
+
+template <int MR, int NR>
+void launch_wgrad_narrow(const WgradParams &p, const WgradPlan &pl, dim3 grid, dim3 block, hipStream_t st) {
+    if (pl.kernel == WG_X3 && pl.h2) RCF_GO(igemm_wgrad_x3_kernel<MR, NR, 2>);
+    else if (pl.kernel == WG_X3) RCF_GO(igemm_wgrad_x3_kernel<MR, NR, 3>);
+    else RCF_GO_BB(p.Wo >= BK, p.Cin == 4, igemm_wgrad_kernel, MR, NR);      // <MR, NR, INCR, SMALLC>
 }
 
 // the GEMM view of the conv kernels' parameters -- a 1x1 convolution whose "pixels" are the M rows -- after the argument checks
@@ -2401,7 +2423,9 @@ extern "C" int rcf_gemm_nt_f32(const float *A, int lda, const float *B, int ldb,
     // needs the plain layout it was made from (ldb == K)
     if (b_pairs && ldb != K) return RCF_EINVAL;
     p.amax_a = amax_a; p.amax_b = amax_b; p.b_pairs = (amax_a && amax_b) ? b_pairs : nullptr; p.amax_out = amax_out;
-    return launch_igemm_x3(p, rcf_stream(stream));
+    ConvPlan pl;
+    if (int e = plan_conv(p, 1, p.b_pairs != nullptr, pl)) return e;
+    return launch_conv(p, pl, rcf_stream(stream));
 }
 
 /* batch0 x batch1 independent products in one launch (attention: images x heads): operand / result of product (i0, i1)
@@ -2414,24 +2438,22 @@ extern "C" int rcf_gemm_nt_batched_f32(const float *A, int lda, long a_s0, long 
     if (batch0 <= 0 || batch1 <= 0 || (long)batch0 * batch1 > 65535) return RCF_EINVAL;
     if ((a_s0 | a_s1 | b_s0 | b_s1 | c_s0 | c_s1) % 4) return RCF_EINVAL;
     p.batch1 = batch1; p.a_bs0 = a_s0; p.a_bs1 = a_s1; p.b_bs0 = b_s0; p.b_bs1 = b_s1; p.y_bs0 = c_s0; p.y_bs1 = c_s1;
-    return launch_igemm_x3(p, rcf_stream(stream), batch0 * batch1);
+    ConvPlan pl;
+    if (int e = plan_conv(p, batch0 * batch1, false, pl)) return e;
+    return launch_conv(p, pl, rcf_stream(stream));
 }
 
 extern "C" int rcf_conv2d_fwd_f32(const float *x, const float *w, const float *bias, float *y,
                                   const rcf_conv_shape *s, int act, float slope, int beta, void *stream) {
     return rcf_conv2d_fwd_region_f32(x, w, bias, y, s, nullptr, act, slope, beta, stream);
 }
-
 namespace {
-int conv2d_dgrad_impl(const float *dy, const float *w, float *dx, const rcf_conv_shape *s, const rcf_conv_region *region, int beta,
-                      void *workspace, size_t workspace_bytes, void *stream, int *kernel_only, const rcf_bn_bwd_in *bn = nullptr,
-                      double *stats = nullptr, int *mtiles_out = nullptr, const float *add = nullptr, int add_pitch = 0,
-                      const unsigned char *add_mask = nullptr, int dy_band = 0);
-// forward launch; kernel_only: report the kernel the call would take instead (rcf_conv_kernel_of)
-int conv2d_fwd_impl(const float *x, const float *w, const float *bias, float *y, const rcf_conv_shape *s,
-                    const rcf_conv_region *region, int act, float slope, int beta, double *stats, void *stream, int *kernel_only,
-                    int *mtiles_out = nullptr) {
-    IgemmParams p{};
+// Forward and data gradient in three steps: fill the kernel parameters from the call (fwd_params / dgrad_params: argument checks,
+// no decisions), plan (plan_conv), then prepare the weights where the call left that to the launch, and launch (launch_conv).
+// `pl` is the caller's: the fused-statistics entries read the number of partial-sum rows (mtiles) from it.
+int fwd_params(IgemmParams &p, const float *x, const float *w, const float *bias, float *y, const rcf_conv_shape *s,
+               const rcf_conv_region *region, int act, float slope, int beta, double *stats) {
+    if (!use_x3(s->flags) && (region || stats)) return RCF_EINVAL;     // sub-rectangles / fused statistics exist on the default kernels only
     p.flags = s->flags;
     p.A = x; p.Bw = w; p.bias = bias; p.Y = y;
     p.Ncol = s->Cout; p.K = s->R * s->S * s->Cin;
@@ -2449,14 +2471,90 @@ int conv2d_fwd_impl(const float *x, const float *w, const float *bias, float *y,
     p.stats = stats;
     p.amax_out = s->amax_y;
     p.a_split = (s->flags & RCF_CONV_X_PLANES) ? 1 : 0;
-    if (use_x3(s->flags)) {
-        const int e = launch_igemm_x3(p, rcf_stream(stream), 1, kernel_only);
-        if (mtiles_out) *mtiles_out = p.mtiles;
-        return e;
+    return 0;
+}
+
+int conv2d_fwd_impl(const float *x, const float *w, const float *bias, float *y, const rcf_conv_shape *s,
+                    const rcf_conv_region *region, int act, float slope, int beta, double *stats, void *stream, ConvPlan &pl) {
+    IgemmParams p{};
+    if (int e = fwd_params(p, x, w, bias, y, s, region, act, slope, beta, stats)) return e;
+    if (int e = plan_conv(p, 1, p.b_pairs != nullptr, pl)) return e;
+    return launch_conv(p, pl, rcf_stream(stream));
+}
+
+// what a data gradient may fuse into its epilogue: the batch-norm backward sums (bn + stats: rcf_conv2d_dgrad_bnsums_f32), the
+// masked addend (rcf_conv2d_dgrad_add_f32)
+struct DgradFused { const rcf_bn_bwd_in *bn; double *stats; const float *add; int add_pitch; const unsigned char *add_mask; };
+
+int dgrad_params(IgemmParams &p, const float *dy, const float *w, float *dx, const rcf_conv_shape *s, const rcf_conv_region *region,
+                 int dy_band, int beta, const DgradFused &f) {
+    if (s->Cout % 4) return RCF_EINVAL;
+    if (!use_x3(s->flags) && (region || f.bn)) return RCF_EINVAL;
+    p.flags = s->flags;
+    if (dy_band > 0) {                           // the source frame lives in igemm_conv_x3_kernel's tap-list loop
+        p.flags |= RCF_CONV_H2P_NEVER;
+        p.src_band = dy_band;
     }
-    if (region || stats) return RCF_EINVAL;              // sub-rectangles / fused statistics exist on the default kernels only
-    if (kernel_only) { *kernel_only = 0; return 0; }
-    return launch_igemm<0>(p, rcf_stream(stream));
+    if (f.add) {
+        // the masked addend lives in the lean epilogue of the fp16-pair kernels, like the batch-norm sums below
+        if (!dgrad_lean_ok(s) || region || beta || !f.add_mask || f.add_pitch % 4 || f.add_pitch < s->Cin || !rcf_aligned16(f.add))
+            return RCF_EINVAL;
+        p.flags |= RCF_CONV_H2P_NEVER;
+        p.add_src = f.add; p.add_pitch = f.add_pitch; p.add_mask = f.add_mask;
+    }
+    if (f.bn) {
+        // the batch-norm sums come out of the lean epilogue of the 128-row fp16-pair kernels: whole column tiles, the whole tensor,
+        // weights prepared by the caller (the workspace holds the partial sums), not the persistent kernel (its own epilogue)
+        const rcf_bn_bwd_in *bn = f.bn;
+        if (!dgrad_lean_ok(s) || region || !f.stats || !bn->x || !bn->relu_mask || !bn->mean || !bn->invstd || bn->x_pitch % 4 ||
+            bn->x_pitch < s->Cin || !rcf_aligned16(bn->x) || !rcf_aligned16(bn->mean) || !rcf_aligned16(bn->invstd))
+            return RCF_EINVAL;
+        p.flags |= RCF_CONV_H2P_NEVER;
+        p.stats = f.stats;
+        p.bn_x = bn->x; p.bn_x_pitch = bn->x_pitch; p.bn_mask = bn->relu_mask; p.bn_mean = bn->mean; p.bn_invstd = bn->invstd;
+    }
+    p.A = dy; p.Bw = w; p.bias = nullptr; p.Y = dx;
+    p.Ncol = s->Cin; p.K = s->R * s->S * s->Cout;
+    p.Ho = s->H; p.Wo = s->W; p.Hs = s->Ho; p.Ws = s->Wo; p.Cs = s->Cout; p.S = s->S;
+    if (int e = set_region(p, region, s->N, s->H, s->W)) return e;
+    p.up = 1; p.off = s->pad; p.step = -s->dil; p.div = s->stride;
+    p.a_pitch = s->y_pitch; p.a_img_stride = (long)s->Ho * s->Wo * s->y_pitch; p.y_pitch = s->x_pitch;
+    p.ldb = s->R * s->S * s->Cin; p.act = 0; p.slope = 0.f; p.beta = beta;
+    if (!use_x3(s->flags)) return 0;
+    // the default kernels contract against k-contiguous weights wt[c][rs][co]: prepared once per weight update by the caller (with
+    // both operand ranges), or transposed -- and, with the ranges, split -- into the workspace by the launch itself
+    p.ldb = p.K;
+    p.a_split = (s->flags & RCF_CONV_DY_PLANES) ? 1 : 0;
+    p.amax_out = s->amax_y;
+    p.amax_a = s->amax_dy; p.amax_b = s->amax_w;
+    const void *wpt = s->w_pairs2_t ? s->w_pairs2_t : s->w_pairs_t;
+    if (p.amax_a && p.amax_b && wpt) {
+        p.b_pairs = wpt;
+        if (s->w_pairs2_t && pairs2_written(p.K, s->Cout)) p.b_pairs2 = (const char *)wpt + rcf_conv2d_dgrad_workspace_bytes(s);
+    }
+    return 0;
+}
+
+int conv2d_dgrad_impl(const float *dy, const float *w, float *dx, const rcf_conv_shape *s, const rcf_conv_region *region, int dy_band,
+                      int beta, void *workspace, size_t workspace_bytes, void *stream, const DgradFused &f, ConvPlan &pl) {
+    IgemmParams p{};
+    if (int e = dgrad_params(p, dy, w, dx, s, region, dy_band, beta, f)) return e;
+    const bool own_weights = use_x3(s->flags) && !p.b_pairs;
+    if (own_weights && (!workspace || workspace_bytes < rcf_conv2d_dgrad_workspace_bytes(s) || !rcf_aligned16(workspace))) return RCF_EWORKSPACE;
+    if (int e = plan_conv(p, 1, true, pl)) return e;
+    hipStream_t st = rcf_stream(stream);
+    if (own_weights) {                           // one small pre-pass per call, only now that the launch is known to run
+        const dim3 tgrid(rcf_cdiv(s->Cin, 32), rcf_cdiv(s->Cout, 32), s->R * s->S);
+        if (pl.np == 2) {
+            hipLaunchKernelGGL(weight_pairs_kernel<true>, tgrid, dim3(256), 0, st, w, s->amax_w, (_Float16 *)workspace,
+                               s->Cout, s->Cin, s->R * s->S, (int)korder_chunked(s->flags));
+            p.b_pairs = workspace;
+        } else {
+            hipLaunchKernelGGL(weight_transpose_kernel, tgrid, dim3(256), 0, st, w, (float *)workspace, s->Cout, s->Cin, s->R * s->S);
+            p.Bw = (const float *)workspace;
+        }
+    }
+    return launch_conv(p, pl, st);
 }
 }  // namespace
 
@@ -2466,19 +2564,41 @@ extern "C" int rcf_conv2d_fwd_region_f32(const float *x, const float *w, const f
     if (int e = check_shape(s)) return e;
     if (!x || !w || !y || !rcf_aligned16(x) || !rcf_aligned16(w) || !rcf_aligned16(y)) return RCF_EINVAL;
     if (!region && act == 0 && thin_path(s)) return rcf_thin_fwd(x, w, bias, y, s, beta, rcf_stream(stream));
-    return conv2d_fwd_impl(x, w, bias, y, s, region, act, slope, beta, nullptr, stream, nullptr);
+    ConvPlan pl;
+    return conv2d_fwd_impl(x, w, bias, y, s, region, act, slope, beta, nullptr, stream, pl);
 }
 
-/* which kernel family a forward (dgrad = 0) or data-gradient (dgrad = 1) launch with this shape, these operand pointers and
- * flags takes -- 0 the fp32-MFMA kernels, 1 the 128 x 256-tile family, 2 conv_h2p_kernel (persistent LDS-DMA) -- without launching
- * anything: a pure function of its arguments (profiling labels; it replaces a "last kernel" global). */
+/* include/rcf_hip.h: what a conv launch with this shape, these operand pointers and flags will run -- the planners' own answer
+ * (plan_conv, plan_wgrad; csrc/igemm_bf16.hip's for 16-bit tensors), a pure function of its arguments: nothing is launched and no
+ * pointer is read.  The plan of the GEMM kernels: it does not see the entry points' detour of thin 1x1 convs to csrc/thin.hip. */
+extern "C" int rcf_conv_plan_of(const rcf_conv_shape *s, const rcf_conv_region *region, int direction, int storage, rcf_conv_plan *out) {
+    if (!out || direction < 0 || direction > 2) return RCF_EINVAL;
+    if (storage == RCF_BF16) return rcf_conv_plan_bf16(s, region, direction, out);
+    if (storage != RCF_F32 || check_shape(s)) return RCF_EINVAL;
+    if (direction == 2) {
+        if (s->Cout % 4 || !region_ok(region, s->Ho, s->Wo)) return RCF_EINVAL;
+        WgradPlan pl;
+        if (int e = plan_wgrad(s, region, pl)) return e;
+        *out = rcf_conv_plan{pl.kernel, 64 * pl.mr, 64 * pl.nr, pl.splitk};
+        return 0;
+    }
+    IgemmParams p{};
+    ConvPlan pl;
+    if (int e = direction ? dgrad_params(p, nullptr, nullptr, nullptr, s, region, 0, 0, DgradFused{})
+                          : fwd_params(p, nullptr, nullptr, nullptr, nullptr, s, region, 0, 0.f, 0, nullptr)) return e;
+    if (int e = plan_conv(p, 1, direction || p.b_pairs, pl)) return e;
+    *out = rcf_conv_plan{pl.kernel, pl.kernel == RCF_KERNEL_H2P ? 32 : 64 * pl.mr, 64 * pl.nr, 1};
+    return 0;
+}
+
+/* the `kernel` of rcf_conv_plan_of for a forward (dgrad = 0) or data-gradient (dgrad = 1) launch on fp32 tensors.  A data gradient
+ * that would transpose its weights into a workspace answers RCF_EWORKSPACE, as it always has: this query has none to offer
+ * (tests/golden/conv_plans.json pins it). */
 extern "C" int rcf_conv_kernel_of(const rcf_conv_shape *s, const rcf_conv_region *region, int dgrad) {
-    if (check_shape(s)) return RCF_EINVAL;
-    int k = RCF_EINVAL;
-    float dummy = 0.f;
-    const int e = dgrad ? conv2d_dgrad_impl(&dummy, &dummy, &dummy, s, region, 0, &dummy, (size_t)1 << 40, nullptr, &k)
-                        : conv2d_fwd_impl(&dummy, &dummy, nullptr, &dummy, s, region, 0, 0.f, 0, nullptr, nullptr, &k);
-    return e ? e : k;
+    rcf_conv_plan pl;
+    if (int e = rcf_conv_plan_of(s, region, dgrad ? 1 : 0, RCF_F32, &pl)) return e;
+    if (dgrad && use_x3(s->flags) && !((s->w_pairs2_t || s->w_pairs_t) && s->amax_dy && s->amax_w)) return RCF_EWORKSPACE;
+    return pl.kernel;
 }
 
 extern "C" int rcf_absmax_f32(const float *x, long rows, int C, int pitch, unsigned *amax, void *stream) {
@@ -2591,10 +2711,10 @@ extern "C" int rcf_conv2d_fwd_bnstats_f32(const float *x, const float *w, float 
     if (!x || !w || !y || (!sums && !fin) || !rcf_aligned16(x) || !rcf_aligned16(w) || !rcf_aligned16(y)) return RCF_EINVAL;
     if (!use_x3(s->flags)) return RCF_EINVAL;             // the statistics epilogue exists on the default kernels only
     if (!workspace || workspace_bytes < rcf_conv2d_fwd_stats_workspace_bytes(s)) return RCF_EWORKSPACE;
-    int mtiles = 0;
-    if (int e = conv2d_fwd_impl(x, w, nullptr, y, s, nullptr, 0, 0.f, 0, (double *)workspace, stream, nullptr, &mtiles)) return e;
-    return rcf_sum_partials_bn((const double *)workspace, mtiles, s->Cout, sums,
-                               (double *)workspace + (size_t)mtiles * 2 * s->Cout, fin, stream);
+    ConvPlan pl;
+    if (int e = conv2d_fwd_impl(x, w, nullptr, y, s, nullptr, 0, 0.f, 0, (double *)workspace, stream, pl)) return e;
+    return rcf_sum_partials_bn((const double *)workspace, pl.mtiles, s->Cout, sums,
+                               (double *)workspace + (size_t)pl.mtiles * 2 * s->Cout, fin, stream);
 }
 
 extern "C" int rcf_conv2d_fwd_stats_f32(const float *x, const float *w, float *y, const rcf_conv_shape *s, double *sums,
@@ -2626,8 +2746,8 @@ extern "C" int rcf_conv2d_dgrad_region_band_f32(const float *dy, const float *w,
     if (!dy || !w || !dx || !rcf_aligned16(dy) || !rcf_aligned16(w) || !rcf_aligned16(dx)) return RCF_EINVAL;
     if (dy_band < 0 || (dy_band > 0 && (!use_x3(s->flags) || s->stride != 1 || 2 * dy_band >= s->Ho || 2 * dy_band >= s->Wo))) return RCF_EINVAL;
     if (!region && !dy_band && thin_path(s)) return rcf_thin_dgrad(dy, w, dx, s, beta, rcf_stream(stream));
-    return conv2d_dgrad_impl(dy, w, dx, s, region, beta, workspace, workspace_bytes, stream, nullptr, nullptr, nullptr, nullptr, nullptr, 0,
-                             nullptr, dy_band);
+    ConvPlan pl;
+    return conv2d_dgrad_impl(dy, w, dx, s, region, dy_band, beta, workspace, workspace_bytes, stream, DgradFused{}, pl);
 }
 
 extern "C" size_t rcf_conv2d_dgrad_bnsums_workspace_bytes(const rcf_conv_shape *s) {
@@ -2656,85 +2776,13 @@ extern "C" int rcf_conv2d_dgrad_add_f32(const float *dy, const float *w, float *
         return RCF_EINVAL;
     if (!rcf_conv2d_dgrad_bnsums_ok(s)) return RCF_EINVAL;
     if (bn && (!workspace || workspace_bytes < rcf_conv2d_dgrad_bnsums_workspace_bytes(s) || !rcf_aligned16(workspace))) return RCF_EWORKSPACE;
-    int mtiles = 0;
-    if (int e = conv2d_dgrad_impl(dy, w, dx, s, nullptr, beta, nullptr, 0, stream, nullptr, bn, bn ? (double *)workspace : nullptr, &mtiles,
-                                  add, add_pitch, add_mask))
-        return e;
+    ConvPlan pl;
+    const DgradFused fused{bn, bn ? (double *)workspace : nullptr, add, add_pitch, add_mask};
+    if (int e = conv2d_dgrad_impl(dy, w, dx, s, nullptr, 0, beta, nullptr, 0, stream, fused, pl)) return e;
     if (!bn) return 0;
-    return rcf_sum_partials_f64((const double *)workspace, mtiles, 2 * s->Cin, sums2, (double *)workspace + (size_t)mtiles * 2 * s->Cin,
+    return rcf_sum_partials_f64((const double *)workspace, pl.mtiles, 2 * s->Cin, sums2, (double *)workspace + (size_t)pl.mtiles * 2 * s->Cin,
                                 stream);
 }
-
-namespace {
-int conv2d_dgrad_impl(const float *dy, const float *w, float *dx, const rcf_conv_shape *s, const rcf_conv_region *region, int beta,
-                      void *workspace, size_t workspace_bytes, void *stream, int *kernel_only, const rcf_bn_bwd_in *bn, double *stats,
-                      int *mtiles_out, const float *add, int add_pitch, const unsigned char *add_mask, int dy_band) {
-    if (s->Cout % 4) return RCF_EINVAL;
-    IgemmParams p{};
-    p.flags = s->flags;
-    if (dy_band > 0) {                           // the source frame lives in igemm_conv_x3_kernel's tap-list loop
-        p.flags |= RCF_CONV_H2P_NEVER;
-        p.src_band = dy_band;
-    }
-    if (add) {
-        // the masked addend lives in the lean epilogue of the fp16-pair kernels, like the batch-norm sums below
-        if (!dgrad_lean_ok(s) || region || beta || !add_mask || add_pitch % 4 || add_pitch < s->Cin || !rcf_aligned16(add))
-            return RCF_EINVAL;
-        p.flags |= RCF_CONV_H2P_NEVER;
-        p.add_src = add; p.add_pitch = add_pitch; p.add_mask = add_mask;
-    }
-    if (bn) {
-        // the batch-norm sums come out of the lean epilogue of the 128-row fp16-pair kernels: whole column tiles, the whole tensor,
-        // weights prepared by the caller (the workspace holds the partial sums), not the persistent kernel (its own epilogue)
-        if (!dgrad_lean_ok(s) || region || !stats || !bn->x || !bn->relu_mask || !bn->mean || !bn->invstd || bn->x_pitch % 4 ||
-            bn->x_pitch < s->Cin || !rcf_aligned16(bn->x) || !rcf_aligned16(bn->mean) || !rcf_aligned16(bn->invstd))
-            return RCF_EINVAL;
-        p.flags |= RCF_CONV_H2P_NEVER;
-        p.stats = stats;
-        p.bn_x = bn->x; p.bn_x_pitch = bn->x_pitch; p.bn_mask = bn->relu_mask; p.bn_mean = bn->mean; p.bn_invstd = bn->invstd;
-    }
-    p.A = dy; p.Bw = w; p.bias = nullptr; p.Y = dx;
-    p.Ncol = s->Cin; p.K = s->R * s->S * s->Cout;
-    p.Ho = s->H; p.Wo = s->W; p.Hs = s->Ho; p.Ws = s->Wo; p.Cs = s->Cout; p.S = s->S;
-    if (int e = set_region(p, region, s->N, s->H, s->W)) return e;
-    p.up = 1; p.off = s->pad; p.step = -s->dil; p.div = s->stride;
-    p.a_pitch = s->y_pitch; p.a_img_stride = (long)s->Ho * s->Wo * s->y_pitch; p.y_pitch = s->x_pitch;
-    p.ldb = s->R * s->S * s->Cin; p.act = 0; p.slope = 0.f; p.beta = beta;
-    if (use_x3(s->flags)) {
-        // k-contiguous weights for the bf16 operand fetch: wt[c][rs][co] (one small transpose per call)
-        const size_t need = rcf_conv2d_dgrad_workspace_bytes(s);
-        const void *wpt = s->w_pairs2_t ? s->w_pairs2_t : s->w_pairs_t;
-        const bool prepared = wpt && s->amax_dy && s->amax_w;
-        p.a_split = (s->flags & RCF_CONV_DY_PLANES) ? 1 : 0;
-        p.amax_out = s->amax_y;
-        if (!prepared && (!workspace || workspace_bytes < need || !rcf_aligned16(workspace))) return RCF_EWORKSPACE;
-        hipStream_t st = rcf_stream(stream);
-        p.ldb = p.K;
-        p.amax_a = s->amax_dy; p.amax_b = s->amax_w;
-        const dim3 tgrid(rcf_cdiv(s->Cin, 32), rcf_cdiv(s->Cout, 32), s->R * s->S);
-        if (p.amax_a && p.amax_b && wpt) {
-            p.b_pairs = wpt;                               // prepared once per weight update by the caller
-            if (s->w_pairs2_t && pairs2_written(p.K, s->Cout)) p.b_pairs2 = (const char *)wpt + need;
-        } else if (p.amax_a && p.amax_b) {                // fp16 pairs: transposed AND split, once per launch
-            if (!kernel_only)
-                hipLaunchKernelGGL(weight_pairs_kernel<true>, tgrid, dim3(256), 0, st, w, s->amax_w, (_Float16 *)workspace,
-                                   s->Cout, s->Cin, s->R * s->S, (int)korder_chunked(s->flags));
-            p.b_pairs = workspace;
-        } else {
-            if (!kernel_only)
-                hipLaunchKernelGGL(weight_transpose_kernel, tgrid, dim3(256), 0, st, w, (float *)workspace, s->Cout, s->Cin,
-                                   s->R * s->S);
-            p.Bw = (const float *)workspace;
-        }
-        const int e = launch_igemm_x3(p, st, 1, kernel_only);
-        if (mtiles_out) *mtiles_out = p.mtiles;
-        return e;
-    }
-    if (region || bn) return RCF_EINVAL;
-    if (kernel_only) { *kernel_only = 0; return 0; }
-    return launch_igemm<1>(p, rcf_stream(stream));
-}
-}  // namespace
 
 // rcf_common.h: the split-K reduction of both weight gradients (this file's and csrc/igemm_bf16.hip's)
 int rcf_splitk_reduce(const float *ws, float *dw, long n, long split_stride, int splits, int beta, void *stream) {
@@ -2754,9 +2802,9 @@ extern "C" size_t rcf_conv2d_wgrad_workspace_bytes(const rcf_conv_shape *s) {
 extern "C" size_t rcf_conv2d_wgrad_region_workspace_bytes(const rcf_conv_shape *s, const rcf_conv_region *region) {
     if (check_shape(s) || !region_ok(region, s->Ho, s->Wo)) return 0;
     if (!region && thin_path(s)) return rcf_thin_wgrad_workspace_bytes(s);
-    const WgradPlan pl = plan_wgrad(s, region);
-    if (pl.splitk <= 1) return 0;
-    return (size_t)pl.splitk * s->Cout * s->R * s->S * s->Cin * sizeof(float);
+    WgradPlan pl;
+    plan_wgrad(s, region, pl);                   // (sized whether or not the launch has a kernel: plan_wgrad)
+    return wgrad_workspace_bytes(pl.splitk, s);
 }
 
 extern "C" int rcf_conv2d_wgrad_f32(const float *x, const float *dy, float *dw, const rcf_conv_shape *s, int beta,
@@ -2771,87 +2819,35 @@ extern "C" int rcf_conv2d_wgrad_region_f32(const float *x, const float *dy, floa
     if (!x || !dy || !dw || !rcf_aligned16(x) || !rcf_aligned16(dy) || !rcf_aligned16(dw)) return RCF_EINVAL;
     if (s->Cout % 4 || !region_ok(region, s->Ho, s->Wo)) return RCF_EINVAL;
     if (!region && thin_path(s)) return rcf_thin_wgrad(x, dy, dw, s, beta, workspace, workspace_bytes, rcf_stream(stream));
-    const WgradPlan pl = plan_wgrad(s, region);
-    const size_t need = rcf_conv2d_wgrad_region_workspace_bytes(s, region);
-    if (need > 0 && (!workspace || workspace_bytes < need || !rcf_aligned16(workspace))) return RCF_EWORKSPACE;
+    WgradPlan pl;
+    if (int e = plan_wgrad(s, region, pl)) return e;
+    if (pl.splitk > 1 && (!workspace || workspace_bytes < wgrad_workspace_bytes(pl.splitk, s) || !rcf_aligned16(workspace))) return RCF_EWORKSPACE;
     hipStream_t st = rcf_stream(stream);
     WgradParams p{};
     p.X = x; p.DY = dy;
-    p.OUT = pl.splitk > 1 ? (float *)workspace : dw;
-    p.Cout = s->Cout; p.Cin = s->Cin; p.R = s->R; p.S = s->S;
-    p.H = s->H; p.W = s->W; p.Ho = s->Ho; p.Wo = s->Wo; p.stride = s->stride; p.pad = s->pad; p.dil = s->dil;
-    p.x_pitch = s->x_pitch; p.dy_pitch = s->y_pitch;
-    fill_region(p, region, s->N, s->Ho, s->Wo);
-    p.chunk = pl.chunk; p.itiles = pl.itiles; p.jtiles = pl.jtiles;
-    p.split_stride = (long)s->Cout * s->R * s->S * s->Cin; p.beta = beta;
+    fill_wgrad(p, pl, s, region, beta, dw, workspace);
     p.amax_a = s->amax_dy; p.amax_b = s->amax_x;
-    p.xcd_map = (s->flags & RCF_CONV_NO_WGRAD_XCD) ? 0 : 1;
-    const bool smallc = s->Cin == 4;
-    const bool x3 = use_x3(s->flags);
-    if (region && (smallc || !x3)) return RCF_EINVAL;    // sub-rectangles exist on the split-bf16 kernel only
-    const dim3 grid((unsigned)(pl.itiles * pl.jtiles), (unsigned)((smallc || pl.cols) ? 1 : s->R * s->S), (unsigned)pl.splitk);
-    const bool incr = s->Wo >= BK;
-#define RCF_WGRAD_LAUNCH(MRv, NRv)                                                                                \
-    do {                                                                                                          \
-        if (smallc) {                                                                                             \
-            if (incr) hipLaunchKernelGGL((igemm_wgrad_kernel<MRv, NRv, true, true>), grid, dim3(256), 0, st, p);  \
-            else hipLaunchKernelGGL((igemm_wgrad_kernel<MRv, NRv, false, true>), grid, dim3(256), 0, st, p);      \
-        } else {                                                                                                  \
-            if (incr) hipLaunchKernelGGL((igemm_wgrad_kernel<MRv, NRv, true, false>), grid, dim3(256), 0, st, p); \
-            else hipLaunchKernelGGL((igemm_wgrad_kernel<MRv, NRv, false, false>), grid, dim3(256), 0, st, p);     \
-        }                                                                                                         \
-    } while (0)
-    // narrow tiles: the fp32-MFMA kernel is as fast as the bf16 triples; with operand ranges they take the fp16 pairs
-    // like every other conv of the step (same-box A/B: no difference in step time either way)
-    const bool h2 = p.amax_a && p.amax_b;
-    if (s->flags & (RCF_CONV_X_PLANES | RCF_CONV_DY_PLANES)) {
-        // both operands as fp16 pair planes (igemm_h2dw.inc); one of them alone has no kernel
-        const unsigned both = RCF_CONV_X_PLANES | RCF_CONV_DY_PLANES;
-        if ((s->flags & both) != both || !h2 || !x3 || !pl.cols || pl.mr != 2 || s->Cin % 64 || s->Cout % 8 || s->x_pitch != s->Cin ||
-            s->y_pitch != s->Cout)
-            return RCF_EINVAL;
-        if ((long)(pl.chunk / (long)p.rr + 2) * s->H * s->W * s->x_pitch * 4 >= (1L << 31)) return RCF_EINVAL;
-        const bool onetap = s->Cin % (64 * pl.nr) == 0;
-        p.cblocks = onetap && s->R * s->S > 1 && p.xcd_map ? s->Cin / (64 * pl.nr) : 0;
-        if (pl.nr == 4) {
-            if (region && onetap) hipLaunchKernelGGL((igemm_wgrad_h2d_kernel<4, true, true>), grid, dim3(256), 0, st, p);
-            else if (region) hipLaunchKernelGGL((igemm_wgrad_h2d_kernel<4, true, false>), grid, dim3(256), 0, st, p);
-            else if (onetap) hipLaunchKernelGGL((igemm_wgrad_h2d_kernel<4, false, true>), grid, dim3(256), 0, st, p);
-            else hipLaunchKernelGGL((igemm_wgrad_h2d_kernel<4, false, false>), grid, dim3(256), 0, st, p);
-        } else if (onetap) hipLaunchKernelGGL((igemm_wgrad_h2d_kernel<2, false, true>), grid, dim3(256), 0, st, p);
-        else hipLaunchKernelGGL((igemm_wgrad_h2d_kernel<2, false, false>), grid, dim3(256), 0, st, p);
-    } else if (x3 && !smallc && ((pl.mr == 2 && pl.nr >= 2) || region || h2)) {
-        if ((long)(pl.chunk / (long)p.rr + 2) * s->H * s->W * s->x_pitch * 4 >= (1L << 31)) return RCF_EINVAL;
-        if (h2) {            // fp16 pairs
-            if (pl.cols) {
-                const bool onetap = s->Cin % (64 * pl.nr) == 0;
-                p.cblocks = onetap && s->R * s->S > 1 && p.xcd_map ? s->Cin / (64 * pl.nr) : 0;
-                if (pl.mr == 4) {
-                    if (region) hipLaunchKernelGGL((igemm_wgrad_h2t_kernel<4, true, true, 4>), grid, dim3(256), 0, st, p);
-                    else hipLaunchKernelGGL((igemm_wgrad_h2t_kernel<4, false, true, 4>), grid, dim3(256), 0, st, p);
-                } else if (pl.nr == 4) {
-                    if (region && onetap) hipLaunchKernelGGL((igemm_wgrad_h2t_kernel<4, true, true>), grid, dim3(256), 0, st, p);
-                    else if (region) hipLaunchKernelGGL((igemm_wgrad_h2t_kernel<4, true, false>), grid, dim3(256), 0, st, p);
-                    else if (onetap) hipLaunchKernelGGL((igemm_wgrad_h2t_kernel<4, false, true>), grid, dim3(256), 0, st, p);
-                    else hipLaunchKernelGGL((igemm_wgrad_h2t_kernel<4, false, false>), grid, dim3(256), 0, st, p);
-                } else if (onetap) hipLaunchKernelGGL((igemm_wgrad_h2t_kernel<2, false, true>), grid, dim3(256), 0, st, p);
-                else hipLaunchKernelGGL((igemm_wgrad_h2t_kernel<2, false, false>), grid, dim3(256), 0, st, p);
-            }
-            else if (pl.nr == 4) hipLaunchKernelGGL(igemm_wgrad_x3_wide_kernel<2>, grid, dim3(256), 0, st, p);
-            else if (pl.mr == 2 && pl.nr == 2) hipLaunchKernelGGL((igemm_wgrad_x3_kernel<2, 2, 2>), grid, dim3(256), 0, st, p);
-            else if (pl.mr == 2 && pl.nr == 1) hipLaunchKernelGGL((igemm_wgrad_x3_kernel<2, 1, 2>), grid, dim3(256), 0, st, p);
-            else if (pl.mr == 1 && pl.nr == 2) hipLaunchKernelGGL((igemm_wgrad_x3_kernel<1, 2, 2>), grid, dim3(256), 0, st, p);
-            else hipLaunchKernelGGL((igemm_wgrad_x3_kernel<1, 1, 2>), grid, dim3(256), 0, st, p);
-        } else if (pl.nr == 4) hipLaunchKernelGGL(igemm_wgrad_x3_wide_kernel<3>, grid, dim3(256), 0, st, p);
-        else if (pl.mr == 2 && pl.nr == 2) hipLaunchKernelGGL((igemm_wgrad_x3_kernel<2, 2>), grid, dim3(256), 0, st, p);
-        else if (pl.mr == 2 && pl.nr == 1) hipLaunchKernelGGL((igemm_wgrad_x3_kernel<2, 1>), grid, dim3(256), 0, st, p);
-        else if (pl.mr == 1 && pl.nr == 2) hipLaunchKernelGGL((igemm_wgrad_x3_kernel<1, 2>), grid, dim3(256), 0, st, p);
-        else hipLaunchKernelGGL((igemm_wgrad_x3_kernel<1, 1>), grid, dim3(256), 0, st, p);
-    } else if (pl.mr == 2 && pl.nr == 2) RCF_WGRAD_LAUNCH(2, 2);
-    else if (pl.mr == 2 && pl.nr == 1) RCF_WGRAD_LAUNCH(2, 1);
-    else if (pl.mr == 1 && pl.nr == 2) RCF_WGRAD_LAUNCH(1, 2);
-    else RCF_WGRAD_LAUNCH(1, 1);
-#undef RCF_WGRAD_LAUNCH
+    const dim3 grid((unsigned)(pl.itiles * pl.jtiles), (unsigned)((s->Cin == 4 || pl.cols) ? 1 : s->R * s->S), (unsigned)pl.splitk), block(256);
+    const bool reg = region != nullptr;
+    switch (pl.kernel) {                         // (tap, channel) columns: <NR, REGION, ONETAP>; regions come with 256 columns only (plan_wgrad)
+        case WG_H2D:
+            if (pl.nr == 4) RCF_GO_BB(reg, pl.onetap, igemm_wgrad_h2d_kernel, 4); else RCF_GO_B(pl.onetap, igemm_wgrad_h2d_kernel, 2, false);
+            break;
+        case WG_H2T:
+            if (pl.mr == 4 && reg) RCF_GO(igemm_wgrad_h2t_kernel<4, true, true, 4>);            // 256 x 256: one tap per tile by construction
+            else if (pl.mr == 4) RCF_GO(igemm_wgrad_h2t_kernel<4, false, true, 4>);
+            else if (pl.nr == 4) RCF_GO_BB(reg, pl.onetap, igemm_wgrad_h2t_kernel, 4);
+            else RCF_GO_B(pl.onetap, igemm_wgrad_h2t_kernel, 2, false);
+            break;
+        case WG_X3_WIDE:
+            if (pl.h2) RCF_GO(igemm_wgrad_x3_wide_kernel<2>); else RCF_GO(igemm_wgrad_x3_wide_kernel<3>);
+            break;
+        default:                                 // WG_X3, WG_MFMA: the 64- and 128-wide tiles
+            if (pl.mr == 2 && pl.nr == 2) launch_wgrad_narrow<2, 2>(p, pl, grid, block, st);
+            else if (pl.mr == 2) launch_wgrad_narrow<2, 1>(p, pl, grid, block, st);
+            else if (pl.nr == 2) launch_wgrad_narrow<1, 2>(p, pl, grid, block, st);
+            else launch_wgrad_narrow<1, 1>(p, pl, grid, block, st);
+    }
     RCF_LAUNCH_CHECK();
     if (pl.splitk > 1) return rcf_splitk_reduce((const float *)workspace, dw, p.split_stride, p.split_stride, pl.splitk, beta, stream);
     return 0;

@@ -22,6 +22,8 @@ int rcf_sum_partials_bn(const double *partial, int chunks, int C, double *sums, 
 // igemm_conv.hip (splitk_reduce_kernel): dw[n] (+ dw when beta) = the sum of the `splits` partial weight gradients
 // ws[s * split_stride ...], added in a fixed order; n % 4 == 0, 16-byte aligned
 int rcf_splitk_reduce(const float *ws, float *dw, long n, long split_stride, int splits, int beta, void *stream);
+// igemm_bf16.hip: rcf_conv_plan_of (igemm_conv.hip) for storage == RCF_BF16
+int rcf_conv_plan_bf16(const rcf_conv_shape *s, const rcf_conv_region *region, int direction, rcf_conv_plan *out);
 
 // csrc/crf_sort.hip: rocPRIM radix sort / inclusive scan for the sort-based lattice build (csrc/crf.hip)
 size_t rcf_crf_sort_tmp_bytes(size_t n);

@@ -122,15 +122,6 @@ class _Profile:
         e0.record()
         return e1
 
-    def relabel_last(self, which, new):
-        """the launch just bracketed under `which` turned out to run another kernel (the C side picks it): file it under `new`
-        -- or drop it when `new` is not being recorded"""
-        if self.which is None or which not in self.which or not self.records[which]:
-            return
-        rec = self.records[which].pop()
-        if new in self.which:
-            self.records[new].append(rec)
-
     def stop_detail(self):
         """{(family, tag): {launches, flops, ms}}: the brackets of stop(), kept apart by the launch's shape tag
         (tools/layer_table.py)"""
@@ -313,50 +304,49 @@ if os.environ.get("RCF_CONV_FLAGS"):               # e.g. RCF_CONV_FLAGS=0x8 kee
     CONV_FLAGS = int(os.environ["RCF_CONV_FLAGS"], 0)
 
 
-# The profiling family (bench.py FAMILIES_F32 / FAMILIES_BF16) of a conv launch, one rule per direction.  kind: "f32" (fp32
-# tensors), "planes" (fp16 pair planes in), "h16" (16-bit tensors); the fp32 weight gradient also "h2" (operand ranges given).
-def _fwd_family(s, kind):
-    wide = s.Cout > 128              # forward launches of the 128x256-tile kernel instance / of the narrower tiles
-    if kind == "h16":
-        return "conv_bf16_fwd" if wide else "conv_bf16_fwd_narrow"
-    return ("conv_h2d_fwd" if wide else "conv_h2d_fwd_narrow") if kind == "planes" else "conv_x3_128x256" if wide else "conv_fwd_narrow"
+# The profiling family (bench.py FAMILIES_F32 / FAMILIES_BF16) of a conv launch: (direction, kind) -> the names of its wide-tile
+# launches, of the others, and of the launches conv_h2p_kernel takes.  kind: "f32" (fp32 tensors), "planes" (fp16 pair planes in),
+# "h16" (16-bit tensors); the fp32 weight gradient also "h2" (operand ranges given).  Wide is the 256-column tile at unit stride
+# (a strided data gradient is filed with the narrow ones), and for a weight gradient the 256-column tile of that kind's own kernel.
+_FAMILY = {
+    ("fwd", "f32"): ("conv_x3_128x256", "conv_fwd_narrow", "conv_h2p_fwd"),
+    ("fwd", "planes"): ("conv_h2d_fwd", "conv_h2d_fwd_narrow", None),
+    ("fwd", "h16"): ("conv_bf16_fwd", "conv_bf16_fwd_narrow", None),
+    ("dgrad", "f32"): ("conv_dgrad_wide", "conv_dgrad_other", "conv_h2p_dgrad"),
+    ("dgrad", "planes"): ("conv_h2d_dgrad", "conv_h2d_dgrad_narrow", None),
+    ("dgrad", "h16"): ("conv_bf16_dgrad_wide", "conv_bf16_dgrad_other", None),
+    ("wgrad", "f32"): ("conv_wgrad_other", "conv_wgrad_other", None),
+    ("wgrad", "h2"): ("conv_wgrad_h2t4", "conv_wgrad_other", None),
+    ("wgrad", "planes"): ("conv_wgrad_h2d", "conv_wgrad_h2d_narrow", None),
+    ("wgrad", "h16"): ("conv_bf16_wgrad4", "conv_bf16_wgrad_other", None),
+}
+_WIDE_WGRAD = {"h2": _lib.KERNEL_WGRAD_H2T, "planes": _lib.KERNEL_WGRAD_H2D, "h16": _lib.KERNEL_WGRAD_BF16_DMA}
+CONV_FAMILIES = tuple(sorted({n for names in _FAMILY.values() for n in names if n is not None}))
 
 
-def _dgrad_family(s, kind):
-    wide = s.Cin > 128 and s.stride == 1
-    if kind == "h16":
-        return "conv_bf16_dgrad_wide" if wide else "conv_bf16_dgrad_other"
-    return ("conv_h2d_dgrad" if wide else "conv_h2d_dgrad_narrow") if kind == "planes" else "conv_dgrad_wide" if wide else "conv_dgrad_other"
-
-
-def _wgrad_family(s, kind, region):
-    ktot = s.R * s.S * s.Cin                       # plan_wgrad (csrc/igemm_conv.hip, csrc/igemm_bf16.hip): the 128 x 256 tile
-    if kind == "h16":
-        return "conv_bf16_wgrad4" if (region is None and s.Cout >= 64 and ktot >= 256) else "conv_bf16_wgrad_other"
-    if kind == "planes":
-        return "conv_wgrad_h2d" if ktot >= 256 else "conv_wgrad_h2d_narrow"
-    return "conv_wgrad_h2t4" if (kind == "h2" and s.Cin % 64 == 0 and ktot >= 256 and s.Cout >= 64) else "conv_wgrad_other"
+def conv_family(s, direction, kind, region=None):
+    """the family of the launch the library plans for this shape (rcf_conv_plan_of: its own answer, no tile rule is restated
+    here); a launch it refuses raises, as the launch itself will.  region: the tuple the wrappers take, or None"""
+    plan = _lib.ConvPlan()
+    call("rcf_conv_plan_of", byref(s), _region(region), ("fwd", "dgrad", "wgrad").index(direction),
+         _lib.BF16 if kind == "h16" else _lib.F32, byref(plan))
+    wide, other, h2p = _FAMILY[(direction, kind)]
+    if plan.kernel == _lib.KERNEL_H2P:
+        return h2p
+    if direction == "wgrad":
+        # the 16-bit step files its 256-column region launches with the rest (bench.py FAMILIES_BF16: conv_bf16_wgrad4 = whole tensors)
+        is_wide = plan.kernel == _WIDE_WGRAD.get(kind) and plan.tile_cols == 256 and (kind != "h16" or region is None)
+    else:
+        is_wide = plan.tile_cols == 256 and (direction == "fwd" or s.stride == 1)
+    return wide if is_wide else other
 
 
 def _profile_conv(s, direction, kind, region=None, suffix=""):
-    """Opens the profiling bracket of one conv launch (everything its wrapper issues until `_profile_end`); direction: "fwd",
+    """Opens the profiling bracket of one conv launch (everything its wrapper issues until it records the returned event); direction: "fwd",
     "dgrad" or "wgrad".  Wrappers call it only when PROFILE.which is not None: one attribute test while profiling is off.
-    Returns (closing event, family), or None when the launch's family is not being recorded."""
-    if direction == "wgrad":
-        family = _wgrad_family(s, kind, region)
-    else:
-        family = _dgrad_family(s, kind) if direction == "dgrad" else _fwd_family(s, kind)
+    Returns the closing event, or None when the launch's family is not being recorded."""
     px = _region_pixels(region, s.H, s.W) if direction == "dgrad" else _region_pixels(region, s.Ho, s.Wo)
-    end = PROFILE.bracket(family, 2.0 * s.N * px * s.Cout * s.R * s.S * s.Cin, _shape_tag(s, region) + suffix)
-    return None if end is None else (end, family)
-
-
-def _profile_end(rec, relabel=None):
-    """closes the bracket.  relabel = (s, region, dgrad) of a forward / data-gradient launch that may take the persistent kernel
-    (rcf_conv_kernel_of: a pure function of the launch's arguments): it is then filed under that kernel's own family"""
-    rec[0].record()
-    if relabel is not None and _lib.load().rcf_conv_kernel_of(byref(relabel[0]), _region(relabel[1]), relabel[2]) == 2:
-        PROFILE.relabel_last(rec[1], "conv_h2p_dgrad" if relabel[2] else "conv_h2p_fwd")
+    return PROFILE.bracket(conv_family(s, direction, kind, region), 2.0 * s.N * px * s.Cout * s.R * s.S * s.Cin, _shape_tag(s, region) + suffix)
 
 
 def fused_stats_available():
@@ -419,7 +409,7 @@ def _conv2d_fwd(x, w, bias, stride, pad, dil, act, slope, out, beta, region, ama
     else:
         call("rcf_conv2d_fwd_stats_f32", _p(x), _p(weight_rsck(w)), _p(out), byref(s), _p(sums), _p(ws), need, _stream())
     if end is not None:
-        _profile_end(end, None if x_planes else (s, region, 0))
+        end.record()
     return (out, sums) if stats else out
 
 
@@ -468,7 +458,13 @@ def conv2d_dgrad(dy, w, xshape, stride=1, pad=0, dil=1, out=None, beta=0, region
     if fuse:
         need = _lib.load().rcf_conv2d_dgrad_bnsums_workspace_bytes(byref(s))
     ws = workspace(need, dy.device) if need else None
-    end = _profile_conv(s, "dgrad", "planes" if dy_planes else "f32", region) if PROFILE.which is not None else None
+    end = None
+    if PROFILE.which is not None:
+        ps = s
+        if fuse or addend is not None or dy_band:        # launches the library itself keeps off the persistent kernel
+            ps = _lib.ConvShape.from_buffer_copy(s)
+            ps.flags |= _lib.CONV_H2P_NEVER
+        end = _profile_conv(ps, "dgrad", "planes" if dy_planes else "f32", region)
     sums2 = None
     if fuse or addend is not None:
         bn = None
@@ -486,7 +482,7 @@ def conv2d_dgrad(dy, w, xshape, stride=1, pad=0, dil=1, out=None, beta=0, region
         call("rcf_conv2d_dgrad_region_f32", _p(dy), _p(weight_rsck(w)), _p(out), byref(s), _region(region), beta, _p(ws),
              need, _stream())
     if end is not None:
-        _profile_end(end, (s, region, 1) if (not dy_planes and not fuse and addend is None) else None)
+        end.record()
     return (out, sums2) if bn_bwd is not None else out
 
 
@@ -525,7 +521,7 @@ def conv2d_wgrad(x, dy, w_like, dw, stride=1, pad=0, dil=1, beta=1, region=None,
     end = _profile_conv(s, "wgrad", "planes" if planes else ("f32" if amax is None else "h2"), region) if PROFILE.which is not None else None
     call("rcf_conv2d_wgrad_region_f32", _p(x), _p(dy), _p(weight_rsck(dw)), byref(s), reg, beta, _p(ws), need, _stream())
     if end is not None:
-        _profile_end(end)
+        end.record()
     return dw
 
 
@@ -570,7 +566,7 @@ def conv2d_fwd_bf16(x, w, w_bf16=None, bias=None, stride=1, pad=0, dil=1, act=0,
         call("rcf_conv2d_fwd_bf16", _p(x), _p(w_bf16), _p(bias), _p(out), _dt(out), byref(s), _region(region), act, slope, beta,
              _p(sums), _p(ws), need, _stream())
     if end is not None:
-        _profile_end(end)
+        end.record()
     return (out, sums) if stats else out
 
 
@@ -589,7 +585,7 @@ def conv2d_dgrad_bf16(dy, w, xshape, stride=1, pad=0, dil=1, out=None, beta=0, r
     call("rcf_conv2d_dgrad_bf16", _p(dy), _p(weight_rsck(w)), _p(out), byref(s), _region(region), beta, _p(ws), need,
          _stream())
     if end is not None:
-        _profile_end(end)
+        end.record()
     return out
 
 
@@ -604,7 +600,7 @@ def conv2d_wgrad_bf16(x, dy, w_like, dw, stride=1, pad=0, dil=1, beta=1, region=
     end = _profile_conv(s, "wgrad", "h16", region) if PROFILE.which is not None else None
     call("rcf_conv2d_wgrad_bf16", _p(x), _p(dy), _p(weight_rsck(dw)), byref(s), reg, beta, _p(ws), need, _stream())
     if end is not None:
-        _profile_end(end)
+        end.record()
     return dw
 
 
@@ -670,7 +666,7 @@ def conv2d_fwd_affine_bf16(x, w, w_bf16, scale, shift, residual=None, relu=True,
     call("rcf_conv2d_fwd_affine_bf16", _p(x), _p(w_bf16), _p(scale), _p(shift), _p(residual),
          pitch_of(residual) if residual is not None else 0, int(relu), _p(out), _p(bits), byref(s), _stream())
     if end is not None:
-        _profile_end(end)
+        end.record()
     return (out, bits) if want_bits else out
 
 
@@ -715,7 +711,7 @@ def conv2d_dgrad_masked_bf16(dy, w, xshape, w_t_bf16, mask_src, out, beta=0, str
     call("rcf_conv2d_dgrad_masked_bf16", _p(dy), _p(w_t_bf16), _p(out), byref(s), int(beta), _p(mask_src),
          pitch_of(mask_src) if mask_src is not None else 0, _p(mask_bits), _p(cs), _p(ws), need, _stream())
     if end is not None:
-        _profile_end(end)
+        end.record()
     return out, cs
 
 

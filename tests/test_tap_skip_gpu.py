@@ -189,3 +189,29 @@ def test_plain_loop_paths(case, report):
     y, y0 = both(lambda: ops.conv2d_fwd(xg, wg, None, stride, pad, dil, amax=(ax, aw)))
     assert torch.equal(y, y0)
     check64(f"fwd {case}", from_nhwc(y), P["y"], P["y32"], frame_mask(y.shape[1], y.shape[2], 0), report)
+
+
+def test_refused_dgrad_band_writes_nothing():
+    """a source frame on a 7x7 filter is refused -- 49 taps do not fit the tap list's 32-bit mask -- by the launch plan, before the
+    pre-pass that would transpose the weights into the caller's workspace: the status is RCF_EINVAL, and neither dx nor the workspace
+    (exactly rcf_conv2d_dgrad_workspace_bytes, so the refusal is not a workspace one) is written.  The entry point is called
+    directly: ops.call would raise on the status"""
+    from ctypes import byref, c_void_p, sizeof
+    lib = _lib.load()
+    N, H, W, C, k = 1, 12, 12, 16, 7
+    s = _lib.ConvShape(N, H, W, C, H, W, C, k, k, 1, 3, 1, C, C, *([None] * 8), 0, sizeof(_lib.ConvShape))
+    need = lib.rcf_conv2d_dgrad_workspace_bytes(byref(s))
+    assert need == k * k * C * C * 4
+    g = torch.Generator().manual_seed(5)
+    dy, w = torch.randn(N, H, W, C, generator=g).to(DEV), torch.randn(C, k, k, C, generator=g).to(DEV)
+    dx, ws = torch.full((N, H, W, C), -7.25, device=DEV), torch.full((need,), 0xA5, dtype=torch.uint8, device=DEV)
+    dx0, ws0 = dx.clone(), ws.clone()
+    ptr = lambda t: c_void_p(t.data_ptr())
+    st = lib.rcf_conv2d_dgrad_region_band_f32(ptr(dy), ptr(w), ptr(dx), byref(s), None, 1, 0, ptr(ws), need, None)
+    torch.cuda.synchronize()
+    assert st == -1                                                       # RCF_EINVAL
+    assert torch.equal(dx.view(torch.int32), dx0.view(torch.int32)) and torch.equal(ws, ws0)
+    # ... and the same call without the source frame runs (the refusal is the frame's, not the shape's)
+    assert lib.rcf_conv2d_dgrad_region_band_f32(ptr(dy), ptr(w), ptr(dx), byref(s), None, 0, 0, ptr(ws), need, None) == 0
+    torch.cuda.synchronize()
+    assert not torch.equal(dx, dx0) and not torch.equal(ws, ws0)
