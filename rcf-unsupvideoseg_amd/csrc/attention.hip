@@ -40,14 +40,6 @@ __device__ __forceinline__ void split3(const f32x4 v, u32x2 &h, u32x2 &m, u32x2 
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 
-__device__ __forceinline__ int h2_exponent(unsigned amax_bits) {
-    const int e = (int)((amax_bits >> 23) & 0xffu);
-    if (amax_bits == 0u) return 0;
-    const int k = 14 - (e - 127);
-    return k > 100 ? 100 : (k < -100 ? -100 : k);
-}
-__device__ __forceinline__ float pow2f(int k) { return __builtin_bit_cast(float, (unsigned)(127 + k) << 23); }
-
 // the fp16-pair split of csrc/igemm_conv.hip (split2h there): h = fp16(x s), m = fp16(x s - h), through v_fma_mix{lo,hi}_f16
 __device__ __forceinline__ unsigned split2h_pair(float a, float b, float s, unsigned &m) {
     unsigned h;

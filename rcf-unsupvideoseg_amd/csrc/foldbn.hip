@@ -107,17 +107,10 @@ __device__ __forceinline__ void fold_finalize_channel(const FoldFin &f, int c, d
     const double m = sz / f.count;
     double var = centred ? szz / f.count : szz / f.count - m * m;
     if (var < 0) var = 0;
-    const float mf = (float)m, is = (float)(1.0 / sqrt(var + (double)f.eps));
-    f.mean[c] = mf;
-    f.invstd[c] = is;
-    const float a = f.gamma[c] * is;
+    const rcf_bn_consts k = rcf_bn_finalize_channel(c, m, var, f.count, f.eps, f.momentum, f.mean, f.invstd, f.rmean, f.rvar);
+    const float a = f.gamma[c] * k.invstd;
     f.scale[c] = a;
-    f.shift[c] = f.beta[c] - mf * a;
-    if (f.rmean) f.rmean[c] = (1.f - f.momentum) * f.rmean[c] + f.momentum * mf;
-    if (f.rvar) {
-        const double unbiased = f.count > 1 ? var * (f.count / (f.count - 1.0)) : var;
-        f.rvar[c] = (1.f - f.momentum) * f.rvar[c] + f.momentum * (float)unbiased;
-    }
+    f.shift[c] = f.beta[c] - k.mean * a;
 }
 __global__ void __launch_bounds__(256) fold_stats_kernel(const float *__restrict__ Ppart, int Z, const double *__restrict__ A1,
                                                          const float *__restrict__ W, float *__restrict__ P,
@@ -143,7 +136,7 @@ __global__ void __launch_bounds__(256) fold_stats_kernel(const float *__restrict
     }
 }
 
-// bn_finalize_kernel's arithmetic (csrc/bn.hip) plus the folded constants scale = gamma invstd, shift = beta - mean scale: the
+// the library's one finalize (rcf_common.h rcf_bn_finalize_channel) plus the folded constants scale = gamma invstd, shift = beta - mean scale: the
 // SyncBN form (the sums were all-reduced between fold_stats_kernel and this)
 __global__ void fold_finalize_kernel(const double *__restrict__ sums, int C, FoldFin fin) {
     const int c = blockIdx.x * blockDim.x + threadIdx.x;

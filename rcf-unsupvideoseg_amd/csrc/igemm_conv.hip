@@ -409,15 +409,7 @@ __device__ __forceinline__ void split3(const f32x4 v, u32x2 &h, u32x2 &m, u32x2 
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 
-// 2^k with k = 14 - floor(log2(max)), |k| <= 100 (amax: raw bits of a non-negative fp32)
-__device__ __forceinline__ int h2_exponent(unsigned amax_bits) {
-    const int e = (int)((amax_bits >> 23) & 0xffu);
-    if (amax_bits == 0u) return 0;
-    int k = 14 - (e - 127);
-    return k > 100 ? 100 : (k < -100 ? -100 : k);
-}
-__device__ __forceinline__ float pow2f(int k) { return __builtin_bit_cast(float, (unsigned)(127 + k) << 23); }
-
+// (the scale's exponent: h2_exponent / pow2f of rcf_common.h, shared with every producer of pair planes)
 // x * s = h + m + (rest below 2^-22 |x s|), h and m in fp16: h = fp16(x s) (s is a power of two: the product is exact),
 // m = fp16(x s - h) (the difference is exact in fp32).  Two values per register pair through gfx950's mixed-precision FMAs:
 // v_fma_mix{lo,hi}_f16 evaluate fma(fp32, fp32, fp32-or-fp16) in fp32 and round the result once to fp16 into the low /

@@ -55,6 +55,37 @@ __device__ __forceinline__ double wave_sum_d(double v) {
     return v;
 }
 
+// ---- fp16 pair planes (include/rcf_hip.h RCF_CONV_X_PLANES): x * 2^k = h + m with k = 14 - floor(log2(bound)), |k| <= 100
+// (bound: raw bits of a non-negative fp32 -- the tensor's range, or an upper bound of it).  ONE rule for the kernels that write
+// planes (bn.hip) and those that scale and read them (igemm_conv.hip and its .inc files, attention.hip): a producer and a
+// consumer that disagreed would scale by one power of two and read with another, and nothing would fail loudly.
+__device__ __forceinline__ int h2_exponent(unsigned amax_bits) {
+    const int e = (int)((amax_bits >> 23) & 0xffu);
+    if (amax_bits == 0u) return 0;
+    const int k = 14 - (e - 127);
+    return k > 100 ? 100 : (k < -100 ? -100 : k);
+}
+__device__ __forceinline__ float pow2f(int k) { return __builtin_bit_cast(float, (unsigned)(127 + k) << 23); }
+
+// ---- the training-mode batch-norm constants of ONE channel from its batch mean and BIASED variance (fp64) over `count` values:
+// mean and invstd in fp32, the running statistics updated in place (either may be NULL; running_var takes the unbiased variance
+// from two values on).  Every finalize of the library is this function (bn.hip: bn_finalize_kernel, sum_finalize_kernel;
+// foldbn.hip: fold_finalize_channel); how the variance is obtained -- batch_var's one-value rule, the fold's centred sums --
+// stays with the caller.  Returns mean and invstd as stored (the fold derives scale and shift from them).
+struct rcf_bn_consts { float mean, invstd; };
+__device__ __forceinline__ rcf_bn_consts rcf_bn_finalize_channel(int c, double m, double var, double count, float eps, float momentum,
+                                                                 float *mean, float *invstd, float *rmean, float *rvar) {
+    const rcf_bn_consts k{(float)m, (float)(1.0 / sqrt(var + (double)eps))};
+    mean[c] = k.mean;
+    invstd[c] = k.invstd;
+    if (rmean) rmean[c] = (1.f - momentum) * rmean[c] + momentum * k.mean;
+    if (rvar) {
+        const double unbiased = count > 1 ? var * (count / (count - 1.0)) : var;
+        rvar[c] = (1.f - momentum) * rvar[c] + momentum * (float)unbiased;
+    }
+    return k;
+}
+
 // ---- mixed-precision storage (the bf16 training step: BASELINE configs[2]) --------------------------------------------
 // Activations / activation gradients may be stored as bf16 (dtype code RCF_BF16) instead of fp32 (RCF_F32); every kernel
 // computes in fp32.  ld4 / st4 move FOUR consecutive channels (16 B of fp32, 8 B of bf16); bf16 -> fp32 is exact,
