@@ -601,6 +601,47 @@ int rcf_correlation_fwd_f32(const float *x1, const float *x2, float *out, int B,
 int rcf_correlation_bwd_f32(const float *x1, const float *x2, const float *dout, const float *out, float *dx1, float *dx2, int B,
                             int C, int H, int W, int max_disp, float slope, void *stream);
 
+/* ---- unFlowLoss (models/amd/flow_loss.py, models/amd/loss_blocks.py; csrc/unflow.hip) --------------------------------------
+ * One direction of one pyramid level.  im, other f32 [B][3][h][w] (the area-resized frames), flow f32 [B][2][h][w] with batch
+ * stride flow_bstride floats (a channel slice of the [B][4][h][w] pyramid flow is read in place), occ0 f32 [B][1][H0][W0] the
+ * level-0 mask, read at (min(floor(y * float(H0) / h), H0 - 1), the same in x): torch's `nearest`.  With
+ * rec = flow_warp(other, flow, 'border'), x = rec occ, y = im occ, md = ssim_sz in 1..3, n = (2 md + 1)^2:
+ *   loss = ( w_l1 mean_{B,3,h,w} |im - rec| occ + w_ssim mean_{B,3,h-2md,w-2md} clamp((1 - S) / 2, 0, 1)
+ *            + w_ternary mean_{B,1,h,w} T ) / mean_{B,1,h,w} occ                        (a weight <= 0 drops its term)
+ *   S = a1 a2 / (b1 b2),  a1 = 2 mx my + C1, a2 = 2 cxy + C2, b1 = mx^2 + my^2 + C1, b2 = vx + vy + C2 over the window's means and
+ *   biased (co)variances, C1 = 1e-4, C2 = 9e-4;  T at an interior pixel p (the 1-pixel border is 0) = (1/9) sum_k u_k^2 / (0.1 + u_k^2),
+ *   u_k = t(Ix(p+k) - Ix(p)) - t(Iy(p+k) - Iy(p)), t(d) = d / sqrt(0.81 + d^2), I = 255 (0.2989 R + 0.5870 G + 0.1140 B).
+ * fwd: out f32 [5] = loss, the three means (L1, SSIM, ternary), the mask mean (0 -> loss NaN, as the reference's 0 / 0).
+ *   partials: rcf_unflow_photo_partials(B, h, w) doubles (RCF_EWORKSPACE when partials_len is less).
+ * bwd: dflow f32 [B][2][h][w] OVERWRITTEN with (dloss[0] / stats[4]) sum_c d rec_c d sample / d position (the tap differences of
+ *   rcf_flow_warp_bwd_f32; 0 on a clipped coordinate), stats = the forward's out, dloss a device scalar, and
+ *   d rec_q = occ_q ( -w_l1 sign(im - rec) / count_l1  +  sum_{p contains q} A_p + x_q sum B_p + y_q sum C_p  +  ternary ) with, for window p,
+ *   live = 0 < (1 - S) / 2 < 1, wgt = -(1/2) live w_ssim / count_ssim,
+ *   A = wgt (2 my (a2 - a1) / (b1 b2) - 2 mx S (1 / b1 - 1 / b2)) / n,  B = -2 wgt S / (b2 n),  C = 2 wgt a1 / (b1 b2 n);
+ *   the ternary part: 255 (0.2989, 0.5870, 0.1140)_c (w_ternary / (9 B h w)) sum over the 8 neighbours m of q of
+ *   ([m interior] + [q interior]) g'(u) t'(d1), d = I(q) - I(m), g'(u) = 0.2 u / (0.1 + u^2)^2, t'(d) = 0.81 / (0.81 + d^2)^1.5.
+ * Every sum is a gather in a fixed order, no atomics: the same bits on every call.  Nothing synchronises with the host.
+ * smooth: flow / s through smooth_grad_1st (second = 0) or smooth_grad_2nd (1) with im [B][3][h][w]; out f32 [1]; an axis with no
+ *   difference gives the reference's NaN.  partials: 2048 doubles.  bwd: dflow OVERWRITTEN with dloss[0] d out / d flow, sign(0) = 0.
+ * area: adaptive average [B][3][H][W] (batch stride x_bstride floats) -> [B][3][h][w], rows floor(i H / h) .. ceil((i + 1) H / h):
+ *   F.interpolate(mode='area').
+ * RCF_EINVAL before any launch -- sizes first, then pointers: B, h, w, H0 or W0 <= 0, md outside 1..3, h or w under 2 md + 1,
+ * h w or H0 W0 >= 2^30, a batch stride under the tensor's own, second outside {0, 1}; a NULL pointer.
+ * rcf_unflow_geometry: 0 -> rows, 1 -> columns of a workgroup's tile, 2 -> the largest md; 0 otherwise. */
+int rcf_unflow_geometry(int which);
+long rcf_unflow_photo_partials(int B, int h, int w);
+int rcf_unflow_photo_fwd_f32(const float *im, const float *other, const float *flow, long flow_bstride, const float *occ0, int H0,
+                             int W0, int md, float w_l1, float w_ssim, float w_ternary, float *out, double *partials,
+                             long partials_len, int B, int h, int w, void *stream);
+int rcf_unflow_photo_bwd_f32(const float *im, const float *other, const float *flow, long flow_bstride, const float *occ0, int H0,
+                             int W0, int md, float w_l1, float w_ssim, float w_ternary, const float *dloss, const float *stats,
+                             float *dflow, int B, int h, int w, void *stream);
+int rcf_unflow_smooth_fwd_f32(const float *flow, long flow_bstride, const float *im, float alpha, float s, int second, float *out,
+                              double *partials, int B, int h, int w, void *stream);
+int rcf_unflow_smooth_bwd_f32(const float *flow, long flow_bstride, const float *im, float alpha, float s, int second,
+                              const float *dloss, float *dflow, int B, int h, int w, void *stream);
+int rcf_unflow_area_f32(const float *x, long x_bstride, float *out, int B, int H, int W, int h, int w, void *stream);
+
 /* ---- dense CRF (permutohedral mean-field) -------------------------------------------------------
  * Replaces torchcrf_cpp.crf_soft / crf_hard (tools/torchCRF/src/torchcrf.cu:106-149), batched over
  * frames, persistent caller-owned workspace instead of 12 cudaMalloc/cudaFree per frame.

@@ -16,3 +16,4 @@ from .model import RCFModel  # noqa: F401
 from .ops import flow_warp, occu_mask_backward as get_occu_mask_backward  # noqa: F401
 from .ops import occu_mask_bidirection as get_occu_mask_bidirection  # noqa: F401
 from .trainer import Trainer, poly_lr_factor  # noqa: F401
+from .unflow_loss import unFlowLoss  # noqa: F401

@@ -193,6 +193,15 @@ PROTOS = {
     "rcf_correlation_geometry": (c_int, [c_int]),
     "rcf_correlation_fwd_f32": (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_int, c_float, P]),
     "rcf_correlation_bwd_f32": (c_int, [P, P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_float, P]),
+    "rcf_unflow_geometry": (c_int, [c_int]),
+    "rcf_unflow_photo_partials": (c_long, [c_int, c_int, c_int]),
+    "rcf_unflow_photo_fwd_f32": (c_int, [P, P, P, c_long, P, c_int, c_int, c_int, c_float, c_float, c_float, P, P, c_long, c_int, c_int,
+                                         c_int, P]),
+    "rcf_unflow_photo_bwd_f32": (c_int, [P, P, P, c_long, P, c_int, c_int, c_int, c_float, c_float, c_float, P, P, P, c_int, c_int,
+                                         c_int, P]),
+    "rcf_unflow_smooth_fwd_f32": (c_int, [P, c_long, P, c_float, c_float, c_int, P, P, c_int, c_int, c_int, P]),
+    "rcf_unflow_smooth_bwd_f32": (c_int, [P, c_long, P, c_float, c_float, c_int, P, P, c_int, c_int, c_int, P]),
+    "rcf_unflow_area_f32": (c_int, [P, c_long, P, c_int, c_int, c_int, c_int, c_int, P]),
     "rcf_crf_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "rcf_crf_soft": (c_int, [P, P, c_int, c_int, c_int, c_float, c_float, c_float, c_float, c_float, c_int, P, P, P,
                              P, c_size_t, P]),

@@ -1062,6 +1062,109 @@ def correlation_bwd(x1, x2, dout, out=None, max_displacement=4, slope=1.0, need_
     return dx1, dx2
 
 
+# ------------------------------------------------------------------------------- unFlowLoss (csrc/unflow.hip)
+def _unflow_operands(*ts):
+    _need_cuda(*ts)
+    for t in ts:
+        if t is not None and (t.dtype != torch.float32 or t.dim() != 4):
+            raise _lib.RcfHipError(f"the flow loss takes float32 [B, C, H, W] tensors, not {t.dtype} {tuple(t.shape)}")
+
+
+def _flow_slice(flow):
+    """a [B, 2, h, w] flow that may be a channel slice of a wider tensor -> (tensor the kernel reads in place, batch stride)"""
+    B, C, h, w = flow.shape
+    if C != 2:
+        raise _lib.RcfHipError(f"a flow has 2 channels, not {C}")
+    if flow.stride(3) != 1 or flow.stride(2) != w or flow.stride(1) != h * w or (B > 1 and flow.stride(0) < 2 * h * w):
+        flow = flow.contiguous()
+    return flow, (flow.stride(0) if B > 1 else 2 * h * w)
+
+
+def _photo_operands(im, other, flow, occ, md):
+    _unflow_operands(im, other, flow, occ)
+    B, _, h, w = flow.shape
+    if tuple(im.shape) != (B, 3, h, w) or tuple(other.shape) != (B, 3, h, w) or occ.shape[:2] != (B, 1):
+        raise _lib.RcfHipError(f"im and other must be [B, 3, h, w] and occ [B, 1, H0, W0] for a flow {tuple(flow.shape)}: "
+                               f"{tuple(im.shape)}, {tuple(other.shape)}, {tuple(occ.shape)}")
+    if md not in (1, 2, 3):
+        raise _lib.RcfHipError(f"the SSIM half-window is 1, 2 or 3, not {md!r}")
+    if h < 2 * md + 1 or w < 2 * md + 1:
+        raise _lib.RcfHipError(f"a {h} x {w} level is smaller than the {2 * md + 1} x {2 * md + 1} SSIM window")
+    flow, bs = _flow_slice(flow)
+    return im.contiguous(), other.contiguous(), flow, bs, occ.contiguous()
+
+
+def unflow_photo(im, other, flow, occ, md=1, w_l1=0.15, w_ssim=0.85, w_ternary=0.0):
+    """One direction of flow_loss.py's loss_photomatric with rec = flow_warp(other, flow, 'border') formed inside the kernel;
+    occ is the level-0 mask, read by torch's nearest rule.  -> (loss 0-dim, stats [5]: loss, the L1 / SSIM / ternary means, the mask
+    mean; unflow_photo_bwd needs it)"""
+    im, other, flow, bs, occ = _photo_operands(im, other, flow, occ, md)
+    B, _, h, w = flow.shape
+    n = _lib.load().rcf_unflow_photo_partials(B, h, w)
+    stats = torch.empty(5, dtype=torch.float32, device=im.device)
+    partials = torch.empty(max(n, 1), dtype=torch.float64, device=im.device)
+    call("rcf_unflow_photo_fwd_f32", _p(im), _p(other), _p(flow), bs, _p(occ), occ.shape[2], occ.shape[3], int(md), float(w_l1),
+         float(w_ssim), float(w_ternary), _p(stats), _p(partials), n, B, h, w, _stream())
+    return stats[0], stats
+
+
+def unflow_photo_bwd(im, other, flow, occ, stats, dloss, md=1, w_l1=0.15, w_ssim=0.85, w_ternary=0.0):
+    """-> dflow [B, 2, h, w]: dloss (a device scalar) times the gradient of unflow_photo's loss with respect to the flow"""
+    im, other, flow, bs, occ = _photo_operands(im, other, flow, occ, md)
+    _need_cuda(stats, dloss)
+    B, _, h, w = flow.shape
+    dloss = dloss.reshape(1).float()
+    dflow = torch.empty((B, 2, h, w), dtype=torch.float32, device=im.device)
+    call("rcf_unflow_photo_bwd_f32", _p(im), _p(other), _p(flow), bs, _p(occ), occ.shape[2], occ.shape[3], int(md), float(w_l1),
+         float(w_ssim), float(w_ternary), _p(dloss), _p(stats), _p(dflow), B, h, w, _stream())
+    return dflow
+
+
+def _smooth_operands(flow, im):
+    _unflow_operands(flow, im)
+    B, _, h, w = flow.shape
+    if tuple(im.shape) != (B, 3, h, w):
+        raise _lib.RcfHipError(f"im must be [B, 3, h, w] for a flow {tuple(flow.shape)}: {tuple(im.shape)}")
+    flow, bs = _flow_slice(flow)
+    return flow, bs, im.contiguous()
+
+
+def unflow_smooth(flow, im, alpha=10.0, s=1.0, second=False):
+    """smooth_grad_1st / smooth_grad_2nd (loss_blocks.py) of flow / s under the edge weights of im -> 0-dim"""
+    flow, bs, im = _smooth_operands(flow, im)
+    B, _, h, w = flow.shape
+    out = torch.empty(1, dtype=torch.float32, device=im.device)
+    partials = torch.empty(2048, dtype=torch.float64, device=im.device)
+    call("rcf_unflow_smooth_fwd_f32", _p(flow), bs, _p(im), float(alpha), float(s), int(bool(second)), _p(out), _p(partials), B, h, w,
+         _stream())
+    return out[0]
+
+
+def unflow_smooth_bwd(flow, im, dloss, alpha=10.0, s=1.0, second=False):
+    flow, bs, im = _smooth_operands(flow, im)
+    _need_cuda(dloss)
+    B, _, h, w = flow.shape
+    dloss = dloss.reshape(1).float()
+    dflow = torch.empty((B, 2, h, w), dtype=torch.float32, device=im.device)
+    call("rcf_unflow_smooth_bwd_f32", _p(flow), bs, _p(im), float(alpha), float(s), int(bool(second)), _p(dloss), _p(dflow), B, h, w,
+         _stream())
+    return dflow
+
+
+def area_resize(x, size):
+    """F.interpolate(x, size, mode='area') of a [B, 3, H, W] tensor (a channel slice of a frame pair is read in place)"""
+    _unflow_operands(x)
+    B, C, H, W = x.shape
+    if C != 3:
+        raise _lib.RcfHipError(f"area_resize takes 3-channel images, not {C} channels")
+    if x.stride(3) != 1 or x.stride(2) != W or x.stride(1) != H * W or (B > 1 and x.stride(0) < 3 * H * W):
+        x = x.contiguous()
+    h, w = int(size[0]), int(size[1])
+    out = torch.empty((B, 3, h, w), dtype=torch.float32, device=x.device)
+    call("rcf_unflow_area_f32", _p(x), x.stride(0) if B > 1 else 3 * H * W, _p(out), B, H, W, h, w, _stream())
+    return out
+
+
 # ------------------------------------------------------------------------------- optimiser
 def adam_step(param, grad, exp_avg, exp_avg_sq, lr, step, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0,
               grad_scale=1.0):
