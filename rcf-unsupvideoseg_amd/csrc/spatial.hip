@@ -132,14 +132,46 @@ __device__ __forceinline__ bool in_frame(int y, int x, int H, int W, int t) {
     return y < t || y >= H - t || x < t || x >= W - t;
 }
 
-// frame > 0: only the output pixels within `frame` of the border are written
-template <typename T>
-__global__ void __launch_bounds__(256) resize_nhwc_fwd_kernel(const T *__restrict__ x, int x_pitch,
-                                                              T *__restrict__ y, int y_pitch, int N, int Hi,
-                                                              int Wi, int Ho, int Wo, int C, int align, float sh,
-                                                              float sw, int frame) {
-    const int CV = C / 4;
-    const int per_img = frame > 0 ? 2 * frame * Wo + 2 * frame * (Ho - 2 * frame) : Ho * Wo;
+// geometry of one bilinear resize, by value to the general kernels.  frame > 0: the forward writes only the output pixels within
+// `frame` of the border; the backward takes dy as zero outside that frame (and does not read it there)
+struct ResizeGeom {
+    int Hi, Wi, Ho, Wo, C, align;
+    float sh, sw;
+    int frame;
+};
+
+// the bilinear blend, the horizontal blends of the two source rows first: ONE expression tree for every resize of the library
+// (the exact-2x kernels below share its halves between outputs)
+__device__ __forceinline__ float blend(float hy, float ly, float hx, float lx, float v00, float v01, float v10, float v11) {
+    return hy * (hx * v00 + lx * v01) + ly * (hx * v10 + lx * v11);
+}
+
+// output pixel (n, yo, xo), channels cv * V .. + V: the body of both general forward kernels
+template <typename T, int V>
+__device__ __forceinline__ void resize_fwd_pixel(const T *__restrict__ x, int x_pitch, T *__restrict__ y, int y_pitch,
+                                                 const ResizeGeom &g, int n, int yo, int xo, int cv) {
+    int y0, y1, x0, x1;
+    float ly, lx;
+    src_index(yo, g.sh, g.align, g.Hi, y0, y1, ly);
+    src_index(xo, g.sw, g.align, g.Wi, x0, x1, lx);
+    const T *base = x + (long)n * g.Hi * g.Wi * x_pitch + cv * V;
+    const fvec<V> v00 = ldv<T, V>(base + ((long)y0 * g.Wi + x0) * x_pitch), v01 = ldv<T, V>(base + ((long)y0 * g.Wi + x1) * x_pitch);
+    const fvec<V> v10 = ldv<T, V>(base + ((long)y1 * g.Wi + x0) * x_pitch), v11 = ldv<T, V>(base + ((long)y1 * g.Wi + x1) * x_pitch);
+    const float hy = 1.f - ly, hx = 1.f - lx;
+    fvec<V> o;
+#pragma unroll
+    for (int h = 0; h < V / 4; ++h)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) o.q[h][e] = blend(hy, ly, hx, lx, v00.q[h][e], v01.q[h][e], v10.q[h][e], v11.q[h][e]);
+    stv<T, V>(y + (((long)n * g.Ho + yo) * g.Wo + xo) * y_pitch + cv * V, o);
+}
+
+// The grid-stride form (only where the row grid below does not fit: N * Ho > 65535; V = 4).  frame > 0: the walk covers the frame alone
+template <typename T, int V>
+__global__ void __launch_bounds__(256) resize_nhwc_fwd_kernel(const T *__restrict__ x, int x_pitch, T *__restrict__ y,
+                                                              int y_pitch, int N, ResizeGeom g) {
+    const int CV = g.C / V;
+    const int per_img = g.frame > 0 ? 2 * g.frame * g.Wo + 2 * g.frame * (g.Ho - 2 * g.frame) : g.Ho * g.Wo;
     const long total = (long)N * per_img * CV;
     const long step = (long)gridDim.x * blockDim.x;
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += step) {
@@ -148,25 +180,11 @@ __global__ void __launch_bounds__(256) resize_nhwc_fwd_kernel(const T *__restric
         const int q = (int)(t % per_img);
         const int n = (int)(t / per_img);
         int yo, xo;
-        if (frame > 0) frame_yx(q, Ho, Wo, frame, yo, xo);
-        else { yo = q / Wo; xo = q - yo * Wo; }
-        int y0, y1, x0, x1;
-        float ly, lx;
-        src_index(yo, sh, align, Hi, y0, y1, ly);
-        src_index(xo, sw, align, Wi, x0, x1, lx);
-        const T *base = x + (long)n * Hi * Wi * x_pitch + cv * 4;
-        const f32x4 v00 = ld4(base + ((long)y0 * Wi + x0) * x_pitch);
-        const f32x4 v01 = ld4(base + ((long)y0 * Wi + x1) * x_pitch);
-        const f32x4 v10 = ld4(base + ((long)y1 * Wi + x0) * x_pitch);
-        const f32x4 v11 = ld4(base + ((long)y1 * Wi + x1) * x_pitch);
-        const float hy = 1.f - ly, hx = 1.f - lx;
-        f32x4 o;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) o[e] = hy * (hx * v00[e] + lx * v01[e]) + ly * (hx * v10[e] + lx * v11[e]);
-        st4(y + (((long)n * Ho + yo) * Wo + xo) * y_pitch + cv * 4, o);
+        if (g.frame > 0) frame_yx(q, g.Ho, g.Wo, g.frame, yo, xo);
+        else { yo = q / g.Wo; xo = q - yo * g.Wo; }
+        resize_fwd_pixel<T, V>(x, x_pitch, y, y_pitch, g, n, yo, xo, cv);
     }
 }
-
 
 // weights of output index o onto input index `in_idx`
 __device__ __forceinline__ float tap_weight(int o, int in_idx, float scale, int align, int in_size) {
@@ -190,16 +208,75 @@ __device__ __forceinline__ void cand_range(int in_idx, float scale, int align, i
     if (hi > out_size - 1) hi = out_size - 1;
 }
 
-// frame > 0: dy is taken as zero outside the border frame of that thickness (and not read there)
-template <typename T>
-__global__ void __launch_bounds__(256) resize_nhwc_bwd_kernel(const T *__restrict__ dy, int dy_pitch,
-                                                              T *__restrict__ dx, int dx_pitch, int beta, int N,
-                                                              int Hi, int Wi, int Ho, int Wo, int C, int align,
-                                                              float sh, float sw, int frame, int tc) {
+// input pixel (n, yi, xi), channels cv * V .. + V: the body of both general backward kernels.  The terms g * (wy * wx) are added
+// output rows upwards, columns upwards, zero weights skipped; beta: onto what dx holds (old + sum)
+template <typename T, int V>
+__device__ __forceinline__ void resize_bwd_pixel(const T *__restrict__ dy, int dy_pitch, T *__restrict__ dx, int dx_pitch, int beta,
+                                                 const ResizeGeom &g, int n, int yi, int xi, int cv) {
+    const int frame = g.frame;
+    int ylo, yhi, xlo, xhi;
+    cand_range(yi, g.sh, g.align, g.Ho, ylo, yhi);
+    cand_range(xi, g.sw, g.align, g.Wo, xlo, xhi);
+    fvec<V> acc;
+#pragma unroll
+    for (int h = 0; h < V / 4; ++h) acc.q[h] = f32x4{0.f, 0.f, 0.f, 0.f};
+    if (frame > 0 && ylo >= frame && yhi < g.Ho - frame && xlo >= frame && xhi < g.Wo - frame) {
+        // no candidate lies on the frame: nothing reaches this pixel (most of the image)
+        if (!beta) stv<T, V>(dx + (((long)n * g.Hi + yi) * g.Wi + xi) * dx_pitch + cv * V, acc);
+        return;
+    }
+    constexpr int MAXC = 6;                 // candidates per axis handled with weights computed once (2x: 4)
+    if (yhi - ylo < MAXC && xhi - xlo < MAXC) {
+        // the column weights are the same for every candidate row: computed once, not once per (row, column)
+        float wxv[MAXC];
+#pragma unroll
+        for (int k = 0; k < MAXC; ++k) wxv[k] = xlo + k <= xhi ? tap_weight(xlo + k, xi, g.sw, g.align, g.Wi) : 0.f;
+        for (int yo = ylo; yo <= yhi; ++yo) {
+            const float wy = tap_weight(yo, yi, g.sh, g.align, g.Hi);
+            if (wy == 0.f) continue;
+            const T *row = dy + (((long)n * g.Ho + yo) * g.Wo + xlo) * dy_pitch + cv * V;
+#pragma unroll
+            for (int k = 0; k < MAXC; ++k) {
+                if (xlo + k > xhi || wxv[k] == 0.f) continue;
+                if (frame > 0 && !in_frame(yo, xlo + k, g.Ho, g.Wo, frame)) continue;
+                const fvec<V> gv = ldv<T, V>(row + (long)k * dy_pitch);
+                const float w = wy * wxv[k];
+#pragma unroll
+                for (int h = 0; h < V / 4; ++h) acc.q[h] += gv.q[h] * w;
+            }
+        }
+    } else {
+        for (int yo = ylo; yo <= yhi; ++yo) {
+            const float wy = tap_weight(yo, yi, g.sh, g.align, g.Hi);
+            if (wy == 0.f) continue;
+            for (int xo = xlo; xo <= xhi; ++xo) {
+                const float wx = tap_weight(xo, xi, g.sw, g.align, g.Wi);
+                if (wx == 0.f) continue;
+                if (frame > 0 && !in_frame(yo, xo, g.Ho, g.Wo, frame)) continue;
+                const fvec<V> gv = ldv<T, V>(dy + (((long)n * g.Ho + yo) * g.Wo + xo) * dy_pitch + cv * V);
+                const float w = wy * wx;
+#pragma unroll
+                for (int h = 0; h < V / 4; ++h) acc.q[h] += gv.q[h] * w;
+            }
+        }
+    }
+    T *dst = dx + (((long)n * g.Hi + yi) * g.Wi + xi) * dx_pitch + cv * V;
+    if (beta) {
+        const fvec<V> old = ldv<T, V>(dst);
+#pragma unroll
+        for (int h = 0; h < V / 4; ++h) acc.q[h] = old.q[h] + acc.q[h];
+    }
+    stv<T, V>(dst, acc);
+}
+
+// The grid-stride form (only where the row grid below does not fit: N * Hi > 65535; V = 4)
+template <typename T, int V>
+__global__ void __launch_bounds__(256) resize_nhwc_bwd_kernel(const T *__restrict__ dy, int dy_pitch, T *__restrict__ dx,
+                                                              int dx_pitch, int beta, int N, ResizeGeom g, int tc) {
     // tc > 0 (frame > 0 and beta != 0): only the input pixels within tc of the border can receive anything from the
     // frame -- the walk covers that input frame alone; the interior keeps what it holds
-    const int CV = C / 4;
-    const long per_img = tc > 0 ? 2L * tc * Wi + 2L * tc * (Hi - 2 * tc) : (long)Hi * Wi;
+    const int CV = g.C / V;
+    const long per_img = tc > 0 ? 2L * tc * g.Wi + 2L * tc * (g.Hi - 2 * tc) : (long)g.Hi * g.Wi;
     const long total = (long)N * per_img * CV;
     const long step = (long)gridDim.x * blockDim.x;
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += step) {
@@ -209,85 +286,40 @@ __global__ void __launch_bounds__(256) resize_nhwc_bwd_kernel(const T *__restric
         const int n = (int)(t / per_img);
         int xi, yi;
         if (tc > 0) {
-            frame_yx(q, Hi, Wi, tc, yi, xi);
+            frame_yx(q, g.Hi, g.Wi, tc, yi, xi);
         } else {
-            yi = q / Wi;
-            xi = q - yi * Wi;
+            yi = q / g.Wi;
+            xi = q - yi * g.Wi;
         }
-        int ylo, yhi, xlo, xhi;
-        cand_range(yi, sh, align, Ho, ylo, yhi);
-        cand_range(xi, sw, align, Wo, xlo, xhi);
-        f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-        if (frame > 0 && ylo >= frame && yhi < Ho - frame && xlo >= frame && xhi < Wo - frame) {
-            // no candidate lies on the frame: nothing reaches this pixel (most of the image)
-            if (!beta) st4(dx + (((long)n * Hi + yi) * Wi + xi) * dx_pitch + cv * 4, acc);
-            continue;
-        }
-        constexpr int MAXC = 6;                 // candidates per axis handled with weights computed once (2x: 4)
-        if (yhi - ylo < MAXC && xhi - xlo < MAXC) {
-            // the column weights are the same for every candidate row: computed once, not once per (row, column)
-            float wxv[MAXC];
-#pragma unroll
-            for (int k = 0; k < MAXC; ++k) wxv[k] = xlo + k <= xhi ? tap_weight(xlo + k, xi, sw, align, Wi) : 0.f;
-            for (int yo = ylo; yo <= yhi; ++yo) {
-                const float wy = tap_weight(yo, yi, sh, align, Hi);
-                if (wy == 0.f) continue;
-                const T *row = dy + (((long)n * Ho + yo) * Wo + xlo) * dy_pitch + cv * 4;
-#pragma unroll
-                for (int k = 0; k < MAXC; ++k) {
-                    if (xlo + k > xhi || wxv[k] == 0.f) continue;
-                    if (frame > 0 && !in_frame(yo, xlo + k, Ho, Wo, frame)) continue;
-                    const f32x4 g = ld4(row + (long)k * dy_pitch);
-                    acc += g * (wy * wxv[k]);
-                }
-            }
-        } else {
-            for (int yo = ylo; yo <= yhi; ++yo) {
-                const float wy = tap_weight(yo, yi, sh, align, Hi);
-                if (wy == 0.f) continue;
-                for (int xo = xlo; xo <= xhi; ++xo) {
-                    const float wx = tap_weight(xo, xi, sw, align, Wi);
-                    if (wx == 0.f) continue;
-                    if (frame > 0 && !in_frame(yo, xo, Ho, Wo, frame)) continue;
-                    const f32x4 g = ld4(dy + (((long)n * Ho + yo) * Wo + xo) * dy_pitch + cv * 4);
-                    acc += g * (wy * wx);
-                }
-            }
-        }
-        T *dst = dx + (((long)n * Hi + yi) * Wi + xi) * dx_pitch + cv * 4;
-        st4(dst, beta ? (ld4(dst) + acc) : acc);
+        resize_bwd_pixel<T, V>(dy, dy_pitch, dx, dx_pitch, beta, g, n, yi, xi, cv);
     }
 }
 
-// Whole-tensor forms (frame == 0) of the two kernels above, which is what the step runs on its large tensors
-// ([16,60,107,256] <-> [16,120,214,256]): blockIdx.y = (image, row), so no thread divides a 64-bit index three times,
-// and V channels per thread (8 = one 16-byte access for bf16).  rocprof before: fwd 221 us, bwd 501 us on that tensor
-// in bf16 (1.2 / 0.5 TB/s of the bytes moved).  Same arithmetic, same order: identical results.
+// The row-grid forms of the two kernels above, which is what a general resize runs on large tensors ([16,60,107,256] <->
+// [16,120,214,256]): blockIdx.y = (image, row), so no thread divides a 64-bit index three times, and V channels per thread
+// (8 = one 16-byte access for bf16).  rocprof before: fwd 221 us, bwd 501 us on that tensor in bf16 (1.2 / 0.5 TB/s of the
+// bytes moved).  The same pixel bodies: identical results.
 template <typename T, int V>
 __global__ void __launch_bounds__(256) resize_rows_fwd_kernel(const T *__restrict__ x, int x_pitch, T *__restrict__ y,
-                                                              int y_pitch, int Hi, int Wi, int Ho, int Wo, int C, int align,
-                                                              float sh, float sw, int frame) {
-    const int CV = C / V;
+                                                              int y_pitch, ResizeGeom g) {
+    const int CV = g.C / V;
     const int idx = blockIdx.x * 256 + threadIdx.x;
     const int xo = idx / CV, cv = idx - xo * CV;
-    if (xo >= Wo) return;
-    const int n = blockIdx.y / Ho, yo = blockIdx.y - n * Ho;
-    if (frame > 0 && !in_frame(yo, xo, Ho, Wo, frame)) return;      // only the border frame is written
-    int y0, y1, x0, x1;
-    float ly, lx;
-    src_index(yo, sh, align, Hi, y0, y1, ly);
-    src_index(xo, sw, align, Wi, x0, x1, lx);
-    const T *base = x + (long)n * Hi * Wi * x_pitch + cv * V;
-    const fvec<V> v00 = ldv<T, V>(base + ((long)y0 * Wi + x0) * x_pitch), v01 = ldv<T, V>(base + ((long)y0 * Wi + x1) * x_pitch);
-    const fvec<V> v10 = ldv<T, V>(base + ((long)y1 * Wi + x0) * x_pitch), v11 = ldv<T, V>(base + ((long)y1 * Wi + x1) * x_pitch);
-    const float hy = 1.f - ly, hx = 1.f - lx;
-    fvec<V> o;
-#pragma unroll
-    for (int h = 0; h < V / 4; ++h)
-#pragma unroll
-        for (int e = 0; e < 4; ++e)
-            o.q[h][e] = hy * (hx * v00.q[h][e] + lx * v01.q[h][e]) + ly * (hx * v10.q[h][e] + lx * v11.q[h][e]);
-    stv<T, V>(y + (((long)n * Ho + yo) * Wo + xo) * y_pitch + cv * V, o);
+    if (xo >= g.Wo) return;
+    const int n = blockIdx.y / g.Ho, yo = blockIdx.y - n * g.Ho;
+    if (g.frame > 0 && !in_frame(yo, xo, g.Ho, g.Wo, g.frame)) return;      // only the border frame is written
+    resize_fwd_pixel<T, V>(x, x_pitch, y, y_pitch, g, n, yo, xo, cv);
+}
+
+template <typename T, int V>
+__global__ void __launch_bounds__(256) resize_rows_bwd_kernel(const T *__restrict__ dy, int dy_pitch, T *__restrict__ dx,
+                                                              int dx_pitch, int beta, ResizeGeom g) {
+    const int CV = g.C / V;
+    const int idx = blockIdx.x * 256 + threadIdx.x;
+    const int xi = idx / CV, cv = idx - xi * CV;
+    if (xi >= g.Wi) return;
+    const int n = blockIdx.y / g.Hi, yi = blockIdx.y - n * g.Hi;
+    resize_bwd_pixel<T, V>(dy, dy_pitch, dx, dx_pitch, beta, g, n, yi, xi, cv);
 }
 
 // Exact 2x up-sampling without align_corners (the decode heads' 60x107 -> 120x214: every bilinear resize of the step): a
@@ -450,69 +482,6 @@ __global__ void __launch_bounds__(256) resize2x_bwd_kernel(const T *__restrict__
         }
 }
 
-template <typename T, int V>
-__global__ void __launch_bounds__(256) resize_rows_bwd_kernel(const T *__restrict__ dy, int dy_pitch, T *__restrict__ dx,
-                                                              int dx_pitch, int beta, int Hi, int Wi, int Ho, int Wo, int C,
-                                                              int align, float sh, float sw, int frame) {
-    const int CV = C / V;
-    const int idx = blockIdx.x * 256 + threadIdx.x;
-    const int xi = idx / CV, cv = idx - xi * CV;
-    if (xi >= Wi) return;
-    const int n = blockIdx.y / Hi, yi = blockIdx.y - n * Hi;
-    int ylo, yhi, xlo, xhi;
-    cand_range(yi, sh, align, Ho, ylo, yhi);
-    cand_range(xi, sw, align, Wo, xlo, xhi);
-    fvec<V> acc;
-#pragma unroll
-    for (int h = 0; h < V / 4; ++h) acc.q[h] = f32x4{0.f, 0.f, 0.f, 0.f};
-    if (frame > 0 && ylo >= frame && yhi < Ho - frame && xlo >= frame && xhi < Wo - frame) {
-        // frame > 0: dy counts as zero off the border frame; no candidate of this pixel lies on it (most of the image)
-        if (!beta) stv<T, V>(dx + (((long)n * Hi + yi) * Wi + xi) * dx_pitch + cv * V, acc);
-        return;
-    }
-    constexpr int MAXC = 6;
-    if (yhi - ylo < MAXC && xhi - xlo < MAXC) {
-        float wxv[MAXC];
-#pragma unroll
-        for (int k = 0; k < MAXC; ++k) wxv[k] = xlo + k <= xhi ? tap_weight(xlo + k, xi, sw, align, Wi) : 0.f;
-        for (int yo = ylo; yo <= yhi; ++yo) {
-            const float wy = tap_weight(yo, yi, sh, align, Hi);
-            if (wy == 0.f) continue;
-            const T *row = dy + (((long)n * Ho + yo) * Wo + xlo) * dy_pitch + cv * V;
-#pragma unroll
-            for (int k = 0; k < MAXC; ++k) {
-                if (xlo + k > xhi || wxv[k] == 0.f) continue;
-                if (frame > 0 && !in_frame(yo, xlo + k, Ho, Wo, frame)) continue;
-                const fvec<V> g = ldv<T, V>(row + (long)k * dy_pitch);
-                const float w = wy * wxv[k];
-#pragma unroll
-                for (int h = 0; h < V / 4; ++h) acc.q[h] += g.q[h] * w;
-            }
-        }
-    } else {
-        for (int yo = ylo; yo <= yhi; ++yo) {
-            const float wy = tap_weight(yo, yi, sh, align, Hi);
-            if (wy == 0.f) continue;
-            for (int xo = xlo; xo <= xhi; ++xo) {
-                const float wx = tap_weight(xo, xi, sw, align, Wi);
-                if (wx == 0.f) continue;
-                if (frame > 0 && !in_frame(yo, xo, Ho, Wo, frame)) continue;
-                const fvec<V> g = ldv<T, V>(dy + (((long)n * Ho + yo) * Wo + xo) * dy_pitch + cv * V);
-                const float w = wy * wx;
-#pragma unroll
-                for (int h = 0; h < V / 4; ++h) acc.q[h] += g.q[h] * w;
-            }
-        }
-    }
-    T *dst = dx + (((long)n * Hi + yi) * Wi + xi) * dx_pitch + cv * V;
-    if (beta) {
-        const fvec<V> old = ldv<T, V>(dst);
-#pragma unroll
-        for (int h = 0; h < V / 4; ++h) acc.q[h] = old.q[h] + acc.q[h];
-    }
-    stv<T, V>(dst, acc);
-}
-
 __global__ void __launch_bounds__(256) resize_nchw_kernel(const float *__restrict__ x, float *__restrict__ y,
                                                           int planes, int Hi, int Wi, int Ho, int Wo, int align,
                                                           float sh, float sw) {
@@ -528,9 +497,7 @@ __global__ void __launch_bounds__(256) resize_nchw_kernel(const float *__restric
         src_index(yo, sh, align, Hi, y0, y1, ly);
         src_index(xo, sw, align, Wi, x0, x1, lx);
         const float *b = x + pl * Hi * Wi;
-        const float hy = 1.f - ly, hx = 1.f - lx;
-        y[i] = hy * (hx * b[(long)y0 * Wi + x0] + lx * b[(long)y0 * Wi + x1]) +
-               ly * (hx * b[(long)y1 * Wi + x0] + lx * b[(long)y1 * Wi + x1]);
+        y[i] = blend(1.f - ly, ly, 1.f - lx, lx, b[(long)y0 * Wi + x0], b[(long)y0 * Wi + x1], b[(long)y1 * Wi + x0], b[(long)y1 * Wi + x1]);
     }
 }
 
@@ -565,20 +532,27 @@ __global__ void __launch_bounds__(256) nhwc_to_nchw_kernel(const float *__restri
     }
 }
 
-// ST -> DT: the same kernel is the fp32 <-> bf16 cast
+// dst[r][c] (+)= src[r][c] over rows x C, four channels per item: items first, first + step, ...  ST -> DT: the same loop is the
+// fp32 <-> bf16 cast.  (first and step are formed in the kernels: formed here, blockDim came by a vector load and the step out of
+// a VGPR multiply -- 7 instructions and 2 VGPRs more per kernel.)
 template <typename ST, typename DT>
-__global__ void __launch_bounds__(256) copy2d_kernel(const ST *__restrict__ src, long spitch,
-                                                     DT *__restrict__ dst, long dpitch, long rows, int C, int beta) {
+__device__ __forceinline__ void copy_rows(const ST *src, long spitch, DT *dst, long dpitch, long rows, int C, int beta, long first,
+                                          long step) {
     const int CV = C / 4;
     const long total = rows * CV;
-    const long step = (long)gridDim.x * blockDim.x;
-    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += step) {
+    for (long i = first; i < total; i += step) {
         const long r = i / CV;
         const int c4 = (int)(i - r * CV) * 4;
         const f32x4 v = ld4(src + r * spitch + c4);
         DT *d = dst + r * dpitch + c4;
         st4(d, beta ? (ld4(d) + v) : v);
     }
+}
+
+template <typename ST, typename DT>
+__global__ void __launch_bounds__(256) copy2d_kernel(const ST *__restrict__ src, long spitch,
+                                                     DT *__restrict__ dst, long dpitch, long rows, int C, int beta) {
+    copy_rows(src, spitch, dst, dpitch, rows, C, beta, (long)blockIdx.x * blockDim.x + threadIdx.x, (long)gridDim.x * blockDim.x);
 }
 
 // n0 x n1 copies in one launch (blockIdx.y = i0 * n1 + i1): copy (i0, i1) starts at src + i0*sb0 + i1*sb1 and
@@ -588,18 +562,8 @@ __global__ void __launch_bounds__(256) copy2d_batched_kernel(const T *__restrict
                                                              T *__restrict__ dst, long dpitch, long db0, long db1,
                                                              long rows, int C, int beta, int n1) {
     const int i0 = blockIdx.y / n1, i1 = blockIdx.y - i0 * n1;
-    src += i0 * sb0 + i1 * sb1;
-    dst += i0 * db0 + i1 * db1;
-    const int CV = C / 4;
-    const long total = rows * CV;
-    const long step = (long)gridDim.x * blockDim.x;
-    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += step) {
-        const long r = i / CV;
-        const int c4 = (int)(i - r * CV) * 4;
-        const f32x4 v = ld4(src + r * spitch + c4);
-        T *d = dst + r * dpitch + c4;
-        st4(d, beta ? (ld4(d) + v) : v);
-    }
+    copy_rows(src + (i0 * sb0 + i1 * sb1), spitch, dst + (i0 * db0 + i1 * db1), dpitch, rows, C, beta,
+              (long)blockIdx.x * blockDim.x + threadIdx.x, (long)gridDim.x * blockDim.x);
 }
 
 // inside[p] = src[p] for pixels in the rectangle, 0 elsewhere; outside[p] = the complement (either may be null)
@@ -675,6 +639,35 @@ extern "C" int rcf_maxpool3x3s2_bwd_f32(const float *dy, const uint8_t *argmax, 
     return rcf_maxpool3x3s2_bwd_mp(dy, argmax, dx, RCF_F32, N, H, W, C, Ho, Wo, stream);
 }
 
+// 8 channels per thread: 16-bit storage whose channel count and both pitches keep every 16-byte access whole
+static inline bool wide8(int dt, int C, int pitch_a, int pitch_b) { return dt == RCF_BF16 && C % 8 == 0 && pitch_a % 8 == 0 && pitch_b % 8 == 0; }
+
+// The launch that ends a resize entry point: KERNEL<T, V> over GRID (which, like the arguments, may name T and V), then the launch
+// check and the return.  RESIZE_LAUNCH4: T by the storage code `dt`, V = 4.  RESIZE_LAUNCH: <bf16_t, 8> where `wide`, else as LAUNCH4.
+#define RESIZE_LAUNCH_AS(T_, V_, KERNEL, GRID, ...)                                                        \
+    {                                                                                                      \
+        using T = T_;                                                                                      \
+        constexpr int V = V_;                                                                              \
+        hipLaunchKernelGGL((KERNEL<T, V>), GRID, dim3(256), 0, rcf_stream(stream), __VA_ARGS__);           \
+    }
+#define RESIZE_LAUNCH4(KERNEL, GRID, ...)                                                                  \
+    do {                                                                                                   \
+        if (dt == RCF_F32) RESIZE_LAUNCH_AS(float, 4, KERNEL, GRID, __VA_ARGS__)                           \
+        else if (dt == RCF_BF16) RESIZE_LAUNCH_AS(bf16_t, 4, KERNEL, GRID, __VA_ARGS__)                    \
+        else return RCF_EINVAL;                                                                            \
+        RCF_LAUNCH_CHECK();                                                                                \
+        return 0;                                                                                          \
+    } while (0)
+#define RESIZE_LAUNCH(KERNEL, GRID, ...)                                                                   \
+    do {                                                                                                   \
+        if (wide) {                                                                                        \
+            RESIZE_LAUNCH_AS(bf16_t, 8, KERNEL, GRID, __VA_ARGS__)                                         \
+            RCF_LAUNCH_CHECK();                                                                            \
+            return 0;                                                                                      \
+        }                                                                                                  \
+        RESIZE_LAUNCH4(KERNEL, GRID, __VA_ARGS__);                                                         \
+    } while (0)
+
 /* frame == 0: the whole tensor; frame == -1: the whole tensor on the general kernel even where the exact-2x form applies (the two
  * are bit-identical: tests) */
 extern "C" int rcf_resize_bilinear_nhwc_fwd_mp(const void *x, int x_pitch, void *y, int y_pitch, int dt, int N, int Hi,
@@ -683,64 +676,23 @@ extern "C" int rcf_resize_bilinear_nhwc_fwd_mp(const void *x, int x_pitch, void 
     const bool general = frame == -1;
     if (general) frame = 0;
     if (frame < 0 || (frame > 0 && (2 * frame >= Ho || 2 * frame >= Wo))) return RCF_EINVAL;
+    const bool wide = wide8(dt, C, x_pitch, y_pitch);
     const long px = frame > 0 ? (long)N * (2L * frame * Wo + 2L * frame * (Ho - 2 * frame)) : (long)N * Ho * Wo;
     if (!general && frame == 0 && !align_corners && Ho == 2 * Hi && Wo == 2 * Wi && Hi >= 2 && Wi >= 2 && (long)N * Hi <= 65535 &&
-        (long)Wi * (C / 4) < (1L << 30)) {
-        if (dt == RCF_BF16 && C % 8 == 0 && x_pitch % 8 == 0 && y_pitch % 8 == 0) {
-            hipLaunchKernelGGL((resize2x_fwd_kernel<bf16_t, 8>), dim3(rcf_cdiv((long)Wi * (C / 8), 256), N * Hi), dim3(256), 0,
-                               rcf_stream(stream), (const bf16_t *)x, x_pitch, (bf16_t *)y, y_pitch, Hi, Wi, C, 0, 0);
-        } else {
-#define RCF_CALL(T)                                                                                                       \
-    hipLaunchKernelGGL((resize2x_fwd_kernel<T, 4>), dim3(rcf_cdiv((long)Wi * (C / 4), 256), N * Hi), dim3(256), 0,         \
-                       rcf_stream(stream), (const T *)x, x_pitch, (T *)y, y_pitch, Hi, Wi, C, 0, 0)
-            RCF_DISPATCH1(dt, RCF_CALL);
-#undef RCF_CALL
-        }
-        RCF_LAUNCH_CHECK();
-        return 0;
-    }
+        (long)Wi * (C / 4) < (1L << 30))
+        RESIZE_LAUNCH(resize2x_fwd_kernel, dim3(rcf_cdiv((long)Wi * (C / V), 256), N * Hi), (const T *)x, x_pitch, (T *)y, y_pitch, Hi,
+                      Wi, C, 0, 0);
     // the border frame of an exact 2x up-sampling (decode_head2's commuted conv): the 2x kernel over the source pixels that reach it
     const int ts = (frame + 1) / 2;
     if (!general && frame > 0 && !align_corners && Ho == 2 * Hi && Wo == 2 * Wi && 2 * ts < Hi && 2 * ts < Wi && N <= 65535 &&
         (long)Wi * Hi * (C / 4) < (1L << 30)) {
         const long Qs = 2L * ts * Wi + 2L * ts * (Hi - 2 * ts);
-        if (dt == RCF_BF16 && C % 8 == 0 && x_pitch % 8 == 0 && y_pitch % 8 == 0) {
-            hipLaunchKernelGGL((resize2x_fwd_kernel<bf16_t, 8>), dim3(rcf_cdiv(Qs * (C / 8), 256), N), dim3(256), 0,
-                               rcf_stream(stream), (const bf16_t *)x, x_pitch, (bf16_t *)y, y_pitch, Hi, Wi, C, frame, ts);
-        } else {
-#define RCF_CALL(T)                                                                                                       \
-    hipLaunchKernelGGL((resize2x_fwd_kernel<T, 4>), dim3(rcf_cdiv(Qs * (C / 4), 256), N), dim3(256), 0,                     \
-                       rcf_stream(stream), (const T *)x, x_pitch, (T *)y, y_pitch, Hi, Wi, C, frame, ts)
-            RCF_DISPATCH1(dt, RCF_CALL);
-#undef RCF_CALL
-        }
-        RCF_LAUNCH_CHECK();
-        return 0;
+        RESIZE_LAUNCH(resize2x_fwd_kernel, dim3(rcf_cdiv(Qs * (C / V), 256), N), (const T *)x, x_pitch, (T *)y, y_pitch, Hi, Wi, C, frame, ts);
     }
-    if ((long)N * Ho <= 65535 && (long)Wo * (C / 4) < (1L << 30)) {
-        const float sh = host_scale(Hi, Ho, align_corners), sw = host_scale(Wi, Wo, align_corners);
-        if (dt == RCF_BF16 && C % 8 == 0 && x_pitch % 8 == 0 && y_pitch % 8 == 0) {
-            hipLaunchKernelGGL((resize_rows_fwd_kernel<bf16_t, 8>), dim3(rcf_cdiv((long)Wo * (C / 8), 256), N * Ho), dim3(256), 0,
-                               rcf_stream(stream), (const bf16_t *)x, x_pitch, (bf16_t *)y, y_pitch, Hi, Wi, Ho, Wo, C,
-                               align_corners, sh, sw, frame);
-        } else {
-#define RCF_CALL(T)                                                                                                       \
-    hipLaunchKernelGGL((resize_rows_fwd_kernel<T, 4>), dim3(rcf_cdiv((long)Wo * (C / 4), 256), N * Ho), dim3(256), 0,      \
-                       rcf_stream(stream), (const T *)x, x_pitch, (T *)y, y_pitch, Hi, Wi, Ho, Wo, C, align_corners, sh, sw, frame)
-            RCF_DISPATCH1(dt, RCF_CALL);
-#undef RCF_CALL
-        }
-        RCF_LAUNCH_CHECK();
-        return 0;
-    }
-#define RCF_CALL(T)                                                                                                    \
-    hipLaunchKernelGGL(resize_nhwc_fwd_kernel<T>, dim3(ew_blocks(px * (C / 4))), dim3(256), 0, rcf_stream(stream),     \
-                       (const T *)x, x_pitch, (T *)y, y_pitch, N, Hi, Wi, Ho, Wo, C, align_corners,                    \
-                       host_scale(Hi, Ho, align_corners), host_scale(Wi, Wo, align_corners), frame)
-    RCF_DISPATCH1(dt, RCF_CALL);
-#undef RCF_CALL
-    RCF_LAUNCH_CHECK();
-    return 0;
+    const ResizeGeom g{Hi, Wi, Ho, Wo, C, align_corners, host_scale(Hi, Ho, align_corners), host_scale(Wi, Wo, align_corners), frame};
+    if ((long)N * Ho <= 65535 && (long)Wo * (C / 4) < (1L << 30))
+        RESIZE_LAUNCH(resize_rows_fwd_kernel, dim3(rcf_cdiv((long)Wo * (C / V), 256), N * Ho), (const T *)x, x_pitch, (T *)y, y_pitch, g);
+    RESIZE_LAUNCH4(resize_nhwc_fwd_kernel, dim3(ew_blocks(px * (C / V))), (const T *)x, x_pitch, (T *)y, y_pitch, N, g);
 }
 extern "C" int rcf_resize_bilinear_nhwc_fwd_f32(const float *x, int x_pitch, float *y, int y_pitch, int N, int Hi,
                                                 int Wi, int Ho, int Wo, int C, int align_corners, void *stream) {
@@ -761,6 +713,7 @@ extern "C" int rcf_resize_bilinear_nhwc_bwd_mp(const void *dy, int dy_pitch, voi
     const bool general = frame == -1;                     // the whole tensor on the general kernel (see the forward)
     if (general) frame = 0;
     if (frame < 0 || (frame > 0 && (2 * frame >= Ho || 2 * frame >= Wo))) return RCF_EINVAL;
+    const bool wide = wide8(dt, C, dy_pitch, dx_pitch);
     // frame > 0: input pixels that can see the output frame lie within tc of the border (conservative: an input pixel's
     // taps lie within (1 + 1/scale) output pixels of its centre); only when the kernel accumulates (beta), otherwise
     // the interior must be written (zeros)
@@ -770,71 +723,31 @@ extern "C" int rcf_resize_bilinear_nhwc_bwd_mp(const void *dy, int dy_pitch, voi
         tc = (int)ceilf(smax * (float)(frame + 2)) + 2;
         if (2 * tc >= Hi || 2 * tc >= Wi) tc = 0;
     }
-    const long items = tc > 0 ? (long)N * (2L * tc * Wi + 2L * tc * (Hi - 2 * tc)) * (C / 4) : (long)N * Hi * Wi * (C / 4);
+    const long px = tc > 0 ? (long)N * (2L * tc * Wi + 2L * tc * (Hi - 2 * tc)) : (long)N * Hi * Wi;
+    const int Hh = (Hi + 1) / 2, Wh = (Wi + 1) / 2;
     if (!general && frame == 0 && !align_corners && Ho == 2 * Hi && Wo == 2 * Wi && Hi >= 2 && Wi >= 2 &&
-        (long)N * ((Hi + 1) / 2) <= 65535 && (long)Wi * (C / 4) < (1L << 30)) {
-        const int Hh = (Hi + 1) / 2, Wh = (Wi + 1) / 2;
-        if (dt == RCF_BF16 && C % 8 == 0 && dy_pitch % 8 == 0 && dx_pitch % 8 == 0) {
-            hipLaunchKernelGGL((resize2x_bwd_kernel<bf16_t, 8>), dim3(rcf_cdiv((long)Wh * (C / 8), 256), N * Hh), dim3(256), 0,
-                               rcf_stream(stream), (const bf16_t *)dy, dy_pitch, (bf16_t *)dx, dx_pitch, beta, Hi, Wi, C, 0, 0);
-        } else {
-#define RCF_CALL(T)                                                                                                       \
-    hipLaunchKernelGGL((resize2x_bwd_kernel<T, 4>), dim3(rcf_cdiv((long)Wh * (C / 4), 256), N * Hh), dim3(256), 0,         \
-                       rcf_stream(stream), (const T *)dy, dy_pitch, (T *)dx, dx_pitch, beta, Hi, Wi, C, 0, 0)
-            RCF_DISPATCH1(dt, RCF_CALL);
-#undef RCF_CALL
-        }
-        RCF_LAUNCH_CHECK();
-        return 0;
-    }
+        (long)N * ((Hi + 1) / 2) <= 65535 && (long)Wi * (C / 4) < (1L << 30))
+        RESIZE_LAUNCH(resize2x_bwd_kernel, dim3(rcf_cdiv((long)Wh * (C / V), 256), N * Hh), (const T *)dy, dy_pitch, (T *)dx, dx_pitch, beta,
+                      Hi, Wi, C, 0, 0);
     // the border frame of an exact 2x up-sampling, accumulating: the 2x kernel over the 2 x 2 input blocks that see the frame -- input
     // rows 0 .. frame / 2 (and their mirror images), i.e. (frame / 2 + 2) / 2 blocks, + 1 for odd sizes (a block that sees no frame
     // pixel adds nothing)
-    {
-        const int Hh = (Hi + 1) / 2, Wh = (Wi + 1) / 2, tb = (frame / 2 + 2) / 2 + 1;
-        if (!general && frame > 0 && beta && !align_corners && Ho == 2 * Hi && Wo == 2 * Wi && 2 * tb < Hh && 2 * tb < Wh && N <= 65535 &&
-            (long)Wh * Hh * (C / 4) < (1L << 30)) {
-            const long Qb = 2L * tb * Wh + 2L * tb * (Hh - 2 * tb);
-            if (dt == RCF_BF16 && C % 8 == 0 && dy_pitch % 8 == 0 && dx_pitch % 8 == 0) {
-                hipLaunchKernelGGL((resize2x_bwd_kernel<bf16_t, 8>), dim3(rcf_cdiv(Qb * (C / 8), 256), N), dim3(256), 0,
-                                   rcf_stream(stream), (const bf16_t *)dy, dy_pitch, (bf16_t *)dx, dx_pitch, beta, Hi, Wi, C, frame, tb);
-            } else {
-#define RCF_CALL(T)                                                                                                       \
-    hipLaunchKernelGGL((resize2x_bwd_kernel<T, 4>), dim3(rcf_cdiv(Qb * (C / 4), 256), N), dim3(256), 0,                     \
-                       rcf_stream(stream), (const T *)dy, dy_pitch, (T *)dx, dx_pitch, beta, Hi, Wi, C, frame, tb)
-                RCF_DISPATCH1(dt, RCF_CALL);
-#undef RCF_CALL
-            }
-            RCF_LAUNCH_CHECK();
-            return 0;
-        }
+    const int tb = (frame / 2 + 2) / 2 + 1;
+    if (!general && frame > 0 && beta && !align_corners && Ho == 2 * Hi && Wo == 2 * Wi && 2 * tb < Hh && 2 * tb < Wh && N <= 65535 &&
+        (long)Wh * Hh * (C / 4) < (1L << 30)) {
+        const long Qb = 2L * tb * Wh + 2L * tb * (Hh - 2 * tb);
+        RESIZE_LAUNCH(resize2x_bwd_kernel, dim3(rcf_cdiv(Qb * (C / V), 256), N), (const T *)dy, dy_pitch, (T *)dx, dx_pitch, beta, Hi, Wi, C,
+                      frame, tb);
     }
-    if ((long)N * Hi <= 65535 && (long)Wi * (C / 4) < (1L << 30)) {
-        const float sh = host_scale(Hi, Ho, align_corners), sw = host_scale(Wi, Wo, align_corners);
-        if (dt == RCF_BF16 && C % 8 == 0 && dy_pitch % 8 == 0 && dx_pitch % 8 == 0) {
-            hipLaunchKernelGGL((resize_rows_bwd_kernel<bf16_t, 8>), dim3(rcf_cdiv((long)Wi * (C / 8), 256), N * Hi), dim3(256), 0,
-                               rcf_stream(stream), (const bf16_t *)dy, dy_pitch, (bf16_t *)dx, dx_pitch, beta, Hi, Wi, Ho, Wo, C,
-                               align_corners, sh, sw, frame);
-        } else {
-#define RCF_CALL(T)                                                                                                       \
-    hipLaunchKernelGGL((resize_rows_bwd_kernel<T, 4>), dim3(rcf_cdiv((long)Wi * (C / 4), 256), N * Hi), dim3(256), 0,      \
-                       rcf_stream(stream), (const T *)dy, dy_pitch, (T *)dx, dx_pitch, beta, Hi, Wi, Ho, Wo, C,             \
-                       align_corners, sh, sw, frame)
-            RCF_DISPATCH1(dt, RCF_CALL);
-#undef RCF_CALL
-        }
-        RCF_LAUNCH_CHECK();
-        return 0;
-    }
-#define RCF_CALL(T)                                                                                                  \
-    hipLaunchKernelGGL(resize_nhwc_bwd_kernel<T>, dim3(ew_blocks(items)), dim3(256), 0, rcf_stream(stream),          \
-                       (const T *)dy, dy_pitch, (T *)dx, dx_pitch, beta, N, Hi, Wi, Ho, Wo, C, align_corners,        \
-                       host_scale(Hi, Ho, align_corners), host_scale(Wi, Wo, align_corners), frame, tc)
-    RCF_DISPATCH1(dt, RCF_CALL);
-#undef RCF_CALL
-    RCF_LAUNCH_CHECK();
-    return 0;
+    const ResizeGeom g{Hi, Wi, Ho, Wo, C, align_corners, host_scale(Hi, Ho, align_corners), host_scale(Wi, Wo, align_corners), frame};
+    if ((long)N * Hi <= 65535 && (long)Wi * (C / 4) < (1L << 30))
+        RESIZE_LAUNCH(resize_rows_bwd_kernel, dim3(rcf_cdiv((long)Wi * (C / V), 256), N * Hi), (const T *)dy, dy_pitch, (T *)dx, dx_pitch,
+                      beta, g);
+    RESIZE_LAUNCH4(resize_nhwc_bwd_kernel, dim3(ew_blocks(px * (C / V))), (const T *)dy, dy_pitch, (T *)dx, dx_pitch, beta, N, g, tc);
 }
+#undef RESIZE_LAUNCH
+#undef RESIZE_LAUNCH4
+#undef RESIZE_LAUNCH_AS
 extern "C" int rcf_resize_bilinear_nhwc_bwd_f32(const float *dy, int dy_pitch, float *dx, int dx_pitch, int beta,
                                                 int N, int Hi, int Wi, int Ho, int Wo, int C, int align_corners,
                                                 void *stream) {
