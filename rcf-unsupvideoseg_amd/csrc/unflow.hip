@@ -11,50 +11,18 @@
 // of LDS.  The four sums of a workgroup go in fp64 into a partials buffer, a one-workgroup finishing kernel adds them in index
 // order.  Backward: x, y on a halo of 2 md, the three SSIM coefficient planes per channel on a halo of md (40 KB at md = 3), then a
 // box sum out of LDS; neither rec nor d rec reaches HBM.  Every result is a gather summed in a fixed order: no atomics, the same
-// bits on every call.  The sample position is float32 in the order of utils/warp_utils.py and grid_sample (csrc/warp.hip:
-// make_taps); the library is compiled without contraction.
+// bits on every call.  The sample position, the blend, the derivative of a sample by its position and the block sum are the
+// ones csrc/warp.hip uses (csrc/flow_sample.h); the library is compiled without contraction.
 //
 // SSIM window sums are taken about the window's centre value (d = x - x_c): the variances then carry the rounding of the
 // differences, not of x^2 ~ 0.25, and a constant window gives sigma = 0 exactly.
-#include "rcf_common.h"
+#include "flow_sample.h"
 
 namespace {
 
 constexpr int UF_TH = 8, UF_TW = 32, UF_MAXMD = 3;      // tile rows, tile columns (256 threads), largest SSIM half-window
 constexpr float UF_C1 = 0.01f * 0.01f, UF_C2 = 0.03f * 0.03f;
 constexpr float UF_GR = 0.2989f, UF_GG = 0.5870f, UF_GB = 0.1140f;
-
-struct UfTap {
-    int o00, o01, o10, o11;     // offsets of the four taps inside a plane (always inside the image)
-    float wx, wy;               // fractional parts
-    bool lx, ly;                // the gradient wrt the coordinate survives the clip
-};
-
-// one axis of norm_grid + grid_sampler_unnormalize(align_corners=True) + clip_coordinates, as tests/warp_cases.py::sample_pos
-__device__ __forceinline__ float uf_pos(float p, int size, bool &live) {
-    const float d = (float)(size - 1);
-    const float g = 2.0f * p / d - 1.0f;
-    float i = ((g + 1.f) / 2.f) * d;
-    live = true;
-    if (!(i > 0.f)) { i = 0.f; live = false; }
-    else if (i >= d) { i = d; live = false; }
-    return i;
-}
-
-__device__ __forceinline__ UfTap uf_tap(int x, int y, float fx, float fy, int W, int H) {
-    UfTap t;
-    const float ix = uf_pos((float)x + fx, W, t.lx), iy = uf_pos((float)y + fy, H, t.ly);
-    const float flx = floorf(ix), fly = floorf(iy);
-    t.wx = ix - flx;
-    t.wy = iy - fly;
-    const int x0 = (int)flx, y0 = (int)fly;             // inside [0, size - 1] after the clip
-    const int x1 = min(x0 + 1, W - 1), y1 = min(y0 + 1, H - 1);      // a tap at `size` has weight exactly 0
-    t.o00 = y0 * W + x0;
-    t.o01 = y0 * W + x1;
-    t.o10 = y1 * W + x0;
-    t.o11 = y1 * W + x1;
-    return t;
-}
 
 __device__ __forceinline__ int uf_near(int dst, float scale, int in) { return min((int)floorf((float)dst * scale), in - 1); }
 
@@ -65,28 +33,27 @@ struct UfImg {
 };
 
 // rec, im and occ of pixel (gy, gx) (inside the image); v[c][k]: the four tap values
-__device__ __forceinline__ void uf_pixel(const UfImg &g, int gy, int gx, UfTap &t, float (&v)[3][4], float (&rec)[3], float (&imv)[3],
+__device__ __forceinline__ void uf_pixel(const UfImg &g, int gy, int gx, Taps &t, float (&v)[3][4], float (&rec)[3], float (&imv)[3],
                                          float &o) {
     const int hw = g.h * g.w, p = gy * g.w + gx;
-    t = uf_tap(gx, gy, g.flow[p], g.flow[hw + p], g.w, g.h);
+    t = make_taps((float)gx + g.flow[p], (float)gy + g.flow[hw + p], g.w, g.h, 0);
+    // taps are read at always-inside offsets: after the clip x0, y0 lie in [0, size - 1], and a tap at `size` has weight exactly 0
+    // and is read at size - 1 (csrc/warp.hip's backward substitutes 0 for the value of a tap outside, so it gathers for itself)
+    const int x1 = min(t.x0 + 1, g.w - 1), y1 = min(t.y0 + 1, g.h - 1);
+    const int o00 = t.y0 * g.w + t.x0, o01 = t.y0 * g.w + x1, o10 = y1 * g.w + t.x0, o11 = y1 * g.w + x1;
     o = g.occ0[uf_near(gy, g.sy, g.H0) * g.W0 + uf_near(gx, g.sx, g.W0)];
     const float ex = 1.f - t.wx, ey = 1.f - t.wy;
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
         const float *pl = g.other + c * hw;
-        v[c][0] = pl[t.o00];
-        v[c][1] = pl[t.o01];
-        v[c][2] = pl[t.o10];
-        v[c][3] = pl[t.o11];
+        v[c][0] = pl[o00];
+        v[c][1] = pl[o01];
+        v[c][2] = pl[o10];
+        v[c][3] = pl[o11];
         imv[c] = g.im[c * hw + p];
     }
 #pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        float r = 0.f;
-        r += v[c][0] * (ey * ex) + v[c][1] * (ey * t.wx);
-        r += v[c][2] * (t.wy * ex) + v[c][3] * (t.wy * t.wx);
-        rec[c] = r;
-    }
+    for (int c = 0; c < 3; ++c) rec[c] = blend4(v[c][0], v[c][1], v[c][2], v[c][3], ey * ex, ey * t.wx, t.wy * ex, t.wy * t.wx);
 }
 
 // the window's means and (co)variances, sums taken about the centre values
@@ -118,20 +85,6 @@ __device__ __forceinline__ void uf_window(const float *X, const float *Y, int pi
 
 __device__ __forceinline__ float uf_gray(const float *X, int plane, int at) {
     return (X[at] * UF_GR + X[plane + at] * UF_GG + X[2 * plane + at] * UF_GB) * 255.f;
-}
-
-// sums of K doubles over the 256 threads, in a fixed order; every thread gets the totals
-template <int K> __device__ __forceinline__ void uf_block_sum(double (&v)[K], double *sh) {
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-        v[k] = wave_sum_d(v[k]);
-        if (lane == 0) sh[wv * K + k] = v[k];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < K; ++k) v[k] = ((sh[k] + sh[K + k]) + sh[2 * K + k]) + sh[3 * K + k];
-    __syncthreads();
 }
 
 __device__ __forceinline__ UfImg uf_image(const float *im, const float *other, const float *flow, long flow_bs, const float *occ0,
@@ -169,7 +122,7 @@ __global__ void __launch_bounds__(256) uf_photo_fwd_kernel(const float *__restri
         const int gy = y0 + ly, gx = x0 + lx;
         float xv[3] = {0.f, 0.f, 0.f}, yv[3] = {0.f, 0.f, 0.f};
         if (gy >= 0 && gy < h && gx >= 0 && gx < w) {
-            UfTap t;
+            Taps t;
             float v[3][4], rec[3], imv[3], o;
             uf_pixel(g, gy, gx, t, v, rec, imv, o);
             float l1 = 0.f;
@@ -220,18 +173,18 @@ __global__ void __launch_bounds__(256) uf_photo_fwd_kernel(const float *__restri
             }
         acc[2] = (double)(s / 9.f);
     }
-    uf_block_sum<4>(acc, red);
+    block_sum_d<4>(acc, red);
     if (threadIdx.x < 4) partials[(long)blockIdx.x * 4 + threadIdx.x] = acc[threadIdx.x];
 }
 
-// partials [n][K] -> tot[K]: thread t adds rows t, t + 256, ... in order, then the fixed tree of uf_block_sum
+// partials [n][K] -> tot[K]: thread t adds rows t, t + 256, ... in order, then the fixed tree of block_sum_d
 template <int K> __device__ __forceinline__ void uf_sum_partials(const double *__restrict__ partials, int n, double (&tot)[K], double *sh) {
 #pragma unroll
     for (int k = 0; k < K; ++k) tot[k] = 0;
     for (int i = (int)threadIdx.x; i < n; i += 256)
 #pragma unroll
         for (int k = 0; k < K; ++k) tot[k] += partials[(long)i * K + k];
-    uf_block_sum<K>(tot, sh);
+    block_sum_d<K>(tot, sh);
 }
 
 // out[0] = the loss, out[1..3] = the three means (L1, SSIM, ternary), out[4] = the mask mean
@@ -284,7 +237,7 @@ __global__ void __launch_bounds__(256) uf_photo_bwd_kernel(const float *__restri
             const int gy = ty0 - 2 * MD + ly, gx = tx0 - 2 * MD + lx;
             float xv[3] = {0.f, 0.f, 0.f}, yv[3] = {0.f, 0.f, 0.f};
             if (gy >= 0 && gy < h && gx >= 0 && gx < w) {
-                UfTap t;
+                Taps t;
                 float v[3][4], rec[3], imv[3], o;
                 uf_pixel(g, gy, gx, t, v, rec, imv, o);
 #pragma unroll
@@ -336,7 +289,7 @@ __global__ void __launch_bounds__(256) uf_photo_bwd_kernel(const float *__restri
     const int tx = (int)threadIdx.x % UF_TW, ty = (int)threadIdx.x / UF_TW;
     const int gy = ty0 + ty, gx = tx0 + tx;
     if (gy >= h || gx >= w) return;
-    UfTap t;
+    Taps t;
     float v[3][4], rec[3], imv[3], o;
     uf_pixel(g, gy, gx, t, v, rec, imv, o);
     float drec[3] = {0.f, 0.f, 0.f};
@@ -390,18 +343,19 @@ __global__ void __launch_bounds__(256) uf_photo_bwd_kernel(const float *__restri
         drec[1] += gi * UF_GG;
         drec[2] += gi * UF_GB;
     }
-    const float ex = 1.f - t.wx, ey = 1.f - t.wy;
     float gix = 0.f, giy = 0.f;
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
-        gix += drec[c] * (ey * (v[c][1] - v[c][0]) + t.wy * (v[c][3] - v[c][2]));
-        giy += drec[c] * (ex * (v[c][2] - v[c][0]) + t.wx * (v[c][3] - v[c][1]));
+        float sx, sy;
+        sample_dpos(v[c][0], v[c][1], v[c][2], v[c][3], t, sx, sy);
+        gix += drec[c] * sx;
+        giy += drec[c] * sy;
     }
     const float scale = dloss[0] / stats[4];
     const long hw = (long)h * w, p = (long)gy * w + gx;
     float *df = dflow + (long)b * 2 * hw;
-    df[p] = t.lx ? scale * gix : 0.f;
-    df[hw + p] = t.ly ? scale * giy : 0.f;
+    df[p] = t.gx_live ? scale * gix : 0.f;
+    df[hw + p] = t.gy_live ? scale * giy : 0.f;
 }
 
 // ---------------------------------------------------------------------------------------------------------------- smoothness
@@ -444,7 +398,7 @@ __global__ void __launch_bounds__(256) uf_smooth_fwd_kernel(const float *__restr
             acc[1] += (double)(second ? wg * t : wg * t / 2.f);
         }
     }
-    uf_block_sum<2>(acc, red);
+    block_sum_d<2>(acc, red);
     if (threadIdx.x < 2) partials[(long)blockIdx.x * 2 + threadIdx.x] = acc[threadIdx.x];
 }
 

@@ -7,8 +7,13 @@
 // per pixel reads the flow once and gathers the 4 taps per channel: 4*(2 + 2*C) algorithmic bytes per
 // pixel (32 B for RGB), HBM-bound, coalesced along x.  Planar NCHW fp32 like the reference API.
 // The normalise / un-normalise round trip of the reference is kept in the same float operations so
-// sample positions round identically.
-#include "rcf_common.h"
+// sample positions round identically: csrc/flow_sample.h holds that arithmetic, the taps and the blend for this file and for
+// csrc/unflow.hip.
+//
+// Kernels: flow_warp_kernel and warp_l1_kernel (per pixel: any channel count, both pad modes; plain warp and fused warp + L1),
+// warp_tile_kernel<L1, E, PX> (RGB / border fast path; plain warp, fused warp + L1 with one or two pixels per lane),
+// flow_warp_bwd_kernel, splat_count_kernel, occ_threshold_kernel, occ_bidir_kernel, photometric_kernel, photometric_final_kernel.
+#include "flow_sample.h"
 
 namespace {
 
@@ -17,77 +22,28 @@ inline int px_blocks(long total) {
     return (int)(b < 1 ? 1 : (b > 16384 ? 16384 : b));
 }
 
-struct Taps {
-    int x0, y0;
-    float wx, wy;     // fractional parts
-    bool inx0, inx1, iny0, iny1;
-    bool gx_live, gy_live;   // gradient wrt coordinate survives clipping
+// element i of a grid-stride walk over [B][H][W] -> image, pixel inside the image, row, column
+struct PixelIdx {
+    long b, p;
+    int py, px;
 };
+__device__ __forceinline__ PixelIdx pixel_index(long i, long HW, int W) {
+    PixelIdx q;
+    q.b = i / HW;
+    q.p = i - q.b * HW;
+    q.py = (int)(q.p / W);
+    q.px = (int)(q.p - (long)q.py * W);
+    return q;
+}
 
-// pad_mode 0 = border, 1 = zeros
-__device__ __forceinline__ Taps make_taps(float px, float py, int W, int H, int pad_mode) {
-    // norm_grid (utils/warp_utils.py:17-24) then grid_sampler_unnormalize(align_corners=True)
-    float gx = 2.0f * px / (float)(W - 1) - 1.0f;
-    float gy = 2.0f * py / (float)(H - 1) - 1.0f;
-    float ix = ((gx + 1.f) / 2.f) * (float)(W - 1);
-    float iy = ((gy + 1.f) / 2.f) * (float)(H - 1);
-    Taps t;
-    t.gx_live = t.gy_live = true;
-    if (pad_mode == 0) {
-        if (!(ix > 0.f)) { ix = 0.f; t.gx_live = false; }
-        else if (ix >= (float)(W - 1)) { ix = (float)(W - 1); t.gx_live = false; }
-        if (!(iy > 0.f)) { iy = 0.f; t.gy_live = false; }
-        else if (iy >= (float)(H - 1)) { iy = (float)(H - 1); t.gy_live = false; }
+// the workgroup's sums of K doubles (fixed order: block_sum_d), added to out[0 .. K) with one fp64 atomic each
+template <int K> __device__ __forceinline__ void block_add(double (&v)[K], double *out) {
+    __shared__ double sh[4 * K];
+    block_sum_d<K>(v, sh);
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int k = 0; k < K; ++k) atomicAdd(out + k, v[k]);
     }
-    const float fx = floorf(ix), fy = floorf(iy);
-    t.wx = ix - fx;
-    t.wy = iy - fy;
-    // huge |flow| -> keep the int conversion defined
-    t.x0 = (int)fminf(fmaxf(fx, -2.f), (float)W + 1.f);
-    t.y0 = (int)fminf(fmaxf(fy, -2.f), (float)H + 1.f);
-    t.inx0 = t.x0 >= 0 && t.x0 < W;
-    t.inx1 = t.x0 + 1 >= 0 && t.x0 + 1 < W;
-    t.iny0 = t.y0 >= 0 && t.y0 < H;
-    t.iny1 = t.y0 + 1 >= 0 && t.y0 + 1 < H;
-    return t;
-}
-
-typedef float f32x2_a4 __attribute__((ext_vector_type(2), aligned(4)));   // 8-byte load, dword aligned
-
-// Branch-free bilinear sample: the two horizontal taps of a row are adjacent, so each row is ONE 8-byte load at a
-// clamped (always valid) position; taps that fall outside the image get weight 0 through selects, never through
-// control flow -- all tap loads of a pixel (2 per channel) issue back to back.
-struct Sampler {
-    int off0, off1;          // float offsets of the two row loads inside a plane
-    float w00, w01, w10, w11;   // weights of (row0: x0, x0+1), (row1: x0, x0+1); 0 for taps outside
-    bool s00, s01;           // which element of the loaded pair is tap x0 / x0+1 (false = [0], true = [1])
-};
-__device__ __forceinline__ Sampler make_sampler(const Taps &t, int W, int H) {
-    Sampler s;
-    const int xb = min(max(t.x0, 0), W - 2);                 // pair base: both elements inside the row
-    const int y0c = min(max(t.y0, 0), H - 1), y1c = min(max(t.y0 + 1, 0), H - 1);
-    s.off0 = y0c * W + xb;
-    s.off1 = y1c * W + xb;
-    s.s00 = t.x0 != xb;                                       // x0 == xb + 1 (only when x0 == W-1)
-    s.s01 = t.x0 + 1 != xb;                                   // false only when x0 == -1
-    const float ex = 1.f - t.wx, ey = 1.f - t.wy;
-    const float m0 = t.inx0 ? 1.f : 0.f, m1 = t.inx1 ? 1.f : 0.f, r0 = t.iny0 ? 1.f : 0.f, r1 = t.iny1 ? 1.f : 0.f;
-    s.w00 = ey * ex * m0 * r0;
-    s.w01 = ey * t.wx * m1 * r0;
-    s.w10 = t.wy * ex * m0 * r1;
-    s.w11 = t.wy * t.wx * m1 * r1;
-    return s;
-}
-__device__ __forceinline__ float sample(const float *__restrict__ plane, const Sampler &s) {
-    const f32x2_a4 a = *reinterpret_cast<const f32x2_a4 *>(plane + s.off0);
-    const f32x2_a4 b = *reinterpret_cast<const f32x2_a4 *>(plane + s.off1);
-    const float a0 = s.s00 ? a[1] : a[0], a1 = s.s01 ? a[1] : a[0];
-    const float b0 = s.s00 ? b[1] : b[0], b1 = s.s01 ? b[1] : b[0];
-    // same order of operations as grid_sample's accumulation: row 0 (x0, x0+1), then row 1
-    float v = 0.f;
-    v += a0 * s.w00 + a1 * s.w01;
-    v += b0 * s.w10 + b1 * s.w11;
-    return v;
 }
 
 // Workgroup -> pixels, XCD aware.  Workgroup id L runs on XCD L % 8, and each XCD has its own L2: an image is cut into 8
@@ -95,10 +51,9 @@ __device__ __forceinline__ float sample(const float *__restrict__ plane, const S
 // run samples are sampled again by the runs above and below it; with runs dealt round-robin to the XCDs
 // every L2 fetched its own copy of those rows (measured: 3.2x the algorithmic fetch bytes), now the same L2 serves them.
 struct BandMap {
-    int b, p0, p1;      // image, first pixel of this workgroup's run, end of its band
+    int b, p0, p1;      // image, first pixel of the run, end of its band
 };
-__device__ __forceinline__ BandMap band_map(int L, int H, int W, int runs_per_band) {
-    const int band = L & 7, slot = L >> 3;
+__device__ __forceinline__ BandMap band_map(int band, int slot, int H, int W, int runs_per_band) {
     const int rb = (H + 7) >> 3;                              // rows per band
     BandMap m;
     m.b = slot / runs_per_band;
@@ -109,11 +64,18 @@ __device__ __forceinline__ BandMap band_map(int L, int H, int W, int runs_per_ba
     return m;
 }
 
+// the sampler of pixel p of an image whose flow is fl
+__device__ __forceinline__ Sampler pixel_sampler(const float *fl, int p, int HW, int W, int H, int pad_mode) {
+    const int py = p / W, px = p - py * W;
+    return make_sampler(make_taps((float)px + fl[p], (float)py + fl[HW + p], W, H, pad_mode), W, H);
+}
+
+// one workgroup per run
 __global__ void __launch_bounds__(256) flow_warp_kernel(const float *__restrict__ x, const float *__restrict__ flow,
                                                         float *__restrict__ out, int B, int C, int H, int W,
                                                         int pad_mode, int runs_per_band) {
     const int HW = H * W;
-    const BandMap bm = band_map(blockIdx.x, H, W, runs_per_band);
+    const BandMap bm = band_map(blockIdx.x & 7, blockIdx.x >> 3, H, W, runs_per_band);
     const long b = bm.b;
     const float *fl = flow + b * 2 * HW;
     const float *xb = x + b * C * HW;
@@ -121,9 +83,7 @@ __global__ void __launch_bounds__(256) flow_warp_kernel(const float *__restrict_
     // a run is 512 pixels: two independent pixels per thread (twice the loads in flight per wavefront)
     const int pa = bm.p0 + threadIdx.x, pb = pa + 256;
     if (C == 3 && pb < bm.p1) {            // RGB: all twelve row loads in flight before the first blend
-        const int ya = pa / W, xa = pa - ya * W, yb = pb / W, xb_ = pb - yb * W;
-        const Sampler sa = make_sampler(make_taps((float)xa + fl[pa], (float)ya + fl[HW + pa], W, H, pad_mode), W, H);
-        const Sampler sb = make_sampler(make_taps((float)xb_ + fl[pb], (float)yb + fl[HW + pb], W, H, pad_mode), W, H);
+        const Sampler sa = pixel_sampler(fl, pa, HW, W, H, pad_mode), sb = pixel_sampler(fl, pb, HW, W, H, pad_mode);
         float va[3], vb[3];
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
@@ -138,10 +98,57 @@ __global__ void __launch_bounds__(256) flow_warp_kernel(const float *__restrict_
         return;
     }
     for (int p = pa; p < bm.p1 && p <= pb; p += 256) {
-        const int py = p / W, px = p - py * W;
-        const Sampler sm = make_sampler(make_taps((float)px + fl[p], (float)py + fl[HW + p], W, H, pad_mode), W, H);
+        const Sampler sm = pixel_sampler(fl, p, HW, W, H, pad_mode);
         for (int c = 0; c < C; ++c) ob[c * HW + p] = sample(xb + c * HW, sm);
     }
+}
+
+// The fused warp + L1 over the same bands and runs: the (image, run) pairs of band k are dealt round-robin to the gridDim.x / 8
+// workgroups of XCD k, so the runs in flight on an XCD at any time are neighbours (their source rows share that L2) while the
+// workgroup count -- each ends in two fp64 atomics -- stays small.  out: sum |im1 - warp(im2)| occ, sum occ
+__global__ void __launch_bounds__(256) warp_l1_kernel(const float *__restrict__ im1, const float *__restrict__ im2,
+                                                      const float *__restrict__ flow, const float *__restrict__ occ,
+                                                      double *__restrict__ out, int B, int C, int H, int W,
+                                                      int pad_mode, int runs_per_band) {
+    const int HW = H * W;
+    const int band = blockIdx.x & 7, Q = gridDim.x >> 3, R = B * runs_per_band;
+    double s[2] = {0, 0};
+    int r = blockIdx.x >> 3;                                  // < Q <= R: the launch gives every workgroup a run
+    do {
+        const BandMap bm = band_map(band, r, H, W, runs_per_band);
+        const long b = bm.b;
+        const float *fl = flow + b * 2 * HW, *src = im2 + b * C * HW, *tgt = im1 + b * C * HW;
+        auto add = [&](int p, float acc) {
+            const float o = occ ? occ[b * HW + p] : 1.f;
+            s[0] += (double)(acc * o);
+            s[1] += (double)o;
+        };
+        // two pixels per trip, as in flow_warp_kernel
+        const int pa = bm.p0 + threadIdx.x, pb = pa + 256;
+        if (C == 3 && pb < bm.p1) {        // RGB: a pixel's nine loads in flight together
+#pragma unroll 1                             // one pixel after the other: unrolled, the compiler interleaves them (68 VGPRs, 7 waves/SIMD)
+            for (int p = pa; p <= pb; p += 256) {
+                const Sampler sm = pixel_sampler(fl, p, HW, W, H, pad_mode);
+                float t[3], w[3], acc = 0.f;
+#pragma unroll
+                for (int c = 0; c < 3; ++c) {
+                    t[c] = tgt[c * HW + p];
+                    w[c] = sample(src + c * HW, sm);
+                }
+#pragma unroll
+                for (int c = 0; c < 3; ++c) acc += fabsf(t[c] - w[c]);
+                add(p, acc);
+            }
+            continue;
+        }
+        for (int p = pa; p < bm.p1 && p <= pb; p += 256) {
+            const Sampler sm = pixel_sampler(fl, p, HW, W, H, pad_mode);
+            float acc = 0.f;
+            for (int c = 0; c < C; ++c) acc += fabsf(tgt[c * HW + p] - sample(src + c * HW, sm));
+            add(p, acc);
+        }
+    } while ((r += Q) < R);
+    block_add(s, out);
 }
 
 __global__ void __launch_bounds__(256) flow_warp_bwd_kernel(const float *__restrict__ x,
@@ -152,10 +159,10 @@ __global__ void __launch_bounds__(256) flow_warp_bwd_kernel(const float *__restr
     const long HW = (long)H * W, total = (long)B * HW;
     const long step = (long)gridDim.x * blockDim.x;
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += step) {
-        const long b = i / HW, p = i - b * HW;
-        const int py = (int)(p / W), px = (int)(p - (long)py * W);
+        const PixelIdx q = pixel_index(i, HW, W);
+        const long b = q.b, p = q.p;
         const float fx = flow[(b * 2) * HW + p], fy = flow[(b * 2 + 1) * HW + p];
-        const Taps t = make_taps((float)px + fx, (float)py + fy, W, H, pad_mode);
+        const Taps t = make_taps((float)q.px + fx, (float)q.py + fy, W, H, pad_mode);
         const float ex = 1.f - t.wx, ey = 1.f - t.wy;
         float gix = 0.f, giy = 0.f;
         for (int c = 0; c < C; ++c) {
@@ -167,8 +174,10 @@ __global__ void __launch_bounds__(256) flow_warp_bwd_kernel(const float *__restr
             if (t.iny0 && t.inx1) { v01 = pl[(long)t.y0 * W + t.x0 + 1]; if (dpl) atomicAdd(dpl + (long)t.y0 * W + t.x0 + 1, g * ey * t.wx); }
             if (t.iny1 && t.inx0) { v10 = pl[(long)(t.y0 + 1) * W + t.x0]; if (dpl) atomicAdd(dpl + (long)(t.y0 + 1) * W + t.x0, g * t.wy * ex); }
             if (t.iny1 && t.inx1) { v11 = pl[(long)(t.y0 + 1) * W + t.x0 + 1]; if (dpl) atomicAdd(dpl + (long)(t.y0 + 1) * W + t.x0 + 1, g * t.wy * t.wx); }
-            gix += g * (ey * (v01 - v00) + t.wy * (v11 - v10));
-            giy += g * (ex * (v10 - v00) + t.wx * (v11 - v01));
+            float sx, sy;
+            sample_dpos(v00, v01, v10, v11, t, sx, sy);
+            gix += g * sx;
+            giy += g * sy;
         }
         if (dflow) {
             dflow[(b * 2) * HW + p] = t.gx_live ? gix : 0.f;
@@ -184,9 +193,9 @@ __global__ void __launch_bounds__(256) splat_count_kernel(const float *__restric
     const long HW = (long)H * W, total = (long)B * HW;
     const long step = (long)gridDim.x * blockDim.x;
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += step) {
-        const long b = i / HW, p = i - b * HW;
-        const int py = (int)(p / W), px = (int)(p - (long)py * W);
-        const float x = (float)px + flow[(b * 2) * HW + p], y = (float)py + flow[(b * 2 + 1) * HW + p];
+        const PixelIdx q = pixel_index(i, HW, W);
+        const long b = q.b, p = q.p;
+        const float x = (float)q.px + flow[(b * 2) * HW + p], y = (float)q.py + flow[(b * 2 + 1) * HW + p];
         const float x1 = floorf(x), y1 = floorf(y);
         const float xf = fminf(fmaxf(x1, 0.f), (float)(W - 1)), yf = fminf(fmaxf(y1, 0.f), (float)(H - 1));
         const float x0 = x1 + 1.f, y0 = y1 + 1.f;
@@ -213,87 +222,15 @@ __global__ void __launch_bounds__(256) occ_bidir_kernel(const float *__restrict_
     const long HW = (long)H * W, total = (long)B * HW;
     const long step = (long)gridDim.x * blockDim.x;
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += step) {
-        const long b = i / HW, p = i - b * HW;
-        const int py = (int)(p / W), px = (int)(p - (long)py * W);
+        const PixelIdx q = pixel_index(i, HW, W);
+        const long b = q.b, p = q.p;
         const float ax = f12[(b * 2) * HW + p], ay = f12[(b * 2 + 1) * HW + p];
-        const Sampler sm = make_sampler(make_taps((float)px + ax, (float)py + ay, W, H, 1), W, H);
+        const Sampler sm = make_sampler(make_taps((float)q.px + ax, (float)q.py + ay, W, H, 1), W, H);
         const float wx = sample(f21 + (b * 2) * HW, sm), wy = sample(f21 + (b * 2 + 1) * HW, sm);
         const float dx = ax + wx, dy = ay + wy;
         const float mag = (ax * ax + ay * ay) + (wx * wx + wy * wy);
         occ[i] = (dx * dx + dy * dy) > scale * mag + bias ? 1.f : 0.f;
     }
-}
-
-__device__ __forceinline__ void block_add2(double a, double b, double *out) {
-    __shared__ double sh[8];
-    a = wave_sum_d(a);
-    b = wave_sum_d(b);
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    if (lane == 0) { sh[w] = a; sh[4 + w] = b; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        atomicAdd(out, sh[0] + sh[1] + sh[2] + sh[3]);
-        atomicAdd(out + 1, sh[4] + sh[5] + sh[6] + sh[7]);
-    }
-    __syncthreads();
-}
-
-__global__ void __launch_bounds__(256) warp_l1_kernel(const float *__restrict__ im1, const float *__restrict__ im2,
-                                                      const float *__restrict__ flow, const float *__restrict__ occ,
-                                                      double *__restrict__ out, int B, int C, int H, int W,
-                                                      int pad_mode, int runs_per_band) {
-    // XCD-aware bands as in flow_warp_kernel.  The (image, 512-pixel run) pairs of band k are dealt round-robin to the
-    // gridDim.x / 8 workgroups of XCD k, so the runs in flight on an XCD at any time are neighbours (their source rows
-    // share that L2) while the workgroup count -- each ends in two fp64 atomics -- stays small.
-    const int HW = H * W;
-    const int band = blockIdx.x & 7, j = blockIdx.x >> 3, Q = gridDim.x >> 3;
-    const int rb = (H + 7) >> 3;
-    const int r0 = min(band * rb, H), r1 = min(r0 + rb, H);
-    const int pend = r1 * W;
-    double s = 0, so = 0;
-    long b = 0;
-    const float *fl = flow;
-    auto pixel = [&](int p, float &acc, float &o) {
-        const int py = p / W, px = p - py * W;
-        const Sampler sm = make_sampler(make_taps((float)px + fl[p], (float)py + fl[HW + p], W, H, pad_mode), W, H);
-        o = occ ? occ[b * HW + p] : 1.f;
-        acc = 0.f;
-        if (C == 3) {                      // RGB: the nine loads in flight together
-            float t[3], w[3];
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                t[c] = im1[(b * 3 + c) * HW + p];
-                w[c] = sample(im2 + (b * 3 + c) * HW, sm);
-            }
-#pragma unroll
-            for (int c = 0; c < 3; ++c) acc += fabsf(t[c] - w[c]);
-        } else {
-            for (int c = 0; c < C; ++c) acc += fabsf(im1[(b * C + c) * HW + p] - sample(im2 + (b * C + c) * HW, sm));
-        }
-    };
-    const int R = B * runs_per_band;
-    for (int r = j; r < R; r += Q) {
-        b = r / runs_per_band;
-        const int run = r - (int)b * runs_per_band;
-        fl = flow + b * 2 * HW;
-        const int p = r0 * W + run * 512 + threadIdx.x;
-        // two independent pixels per trip: twice the loads in flight per wavefront
-        if (p + 256 < pend) {
-            float a0, o0, a1, o1;
-            pixel(p, a0, o0);
-            pixel(p + 256, a1, o1);
-            s += (double)(a0 * o0);
-            so += (double)o0;
-            s += (double)(a1 * o1);
-            so += (double)o1;
-        } else if (p < pend) {
-            float a0, o0;
-            pixel(p, a0, o0);
-            s += (double)(a0 * o0);
-            so += (double)o0;
-        }
-    }
-    block_add2(s, so, out);
 }
 
 // ---- RGB / border fast path ---------------------------------------------------------------------------------------------
@@ -316,7 +253,6 @@ __global__ void __launch_bounds__(256) warp_l1_kernel(const float *__restrict__ 
 // non-temporal loads / stores on the streamed operands (+2 %), 2 or 8 rows per thread (223 / 211 us).  What bounds it
 // now: the texture addresser, 88 % busy (18 dword loads per pixel = 72 requested bytes per 36 algorithmic ones).
 typedef float v2f __attribute__((ext_vector_type(2)));
-typedef float v4f __attribute__((ext_vector_type(4)));
 
 struct WarpGeom {
     float dx, dy, rx, ry;       // W-1, H-1 and their correctly rounded reciprocals
@@ -365,11 +301,28 @@ __device__ __forceinline__ float blend(v2f a, v2f b, const Tap4 &tp) {
     return (ta.x + ta.y) + (tb.x + tb.y);
 }
 
+// E consecutive floats at p (E = 2: one aligned 8-byte load)
+template <int E> __device__ __forceinline__ void stream_load(const float *p, float (&d)[E]) {
+    if constexpr (E == 2) {
+        const v2f t = *reinterpret_cast<const v2f *>(p);
+        d[0] = t.x;
+        d[1] = t.y;
+    } else {
+        d[0] = p[0];
+    }
+}
+
 // XCD k (workgroup ids k mod 8) walks the k-th eighth of the row-major tile list of every image, so the source rows that
-// neighbouring tiles share stay in one L2.  lane = x, wavefront wv takes rows wv, wv+4, ... of the tile.
-constexpr int TILE_W = 64;
-template <bool L1, int PX>
-__global__ void __launch_bounds__(256) warp_rows_kernel(const float *__restrict__ im1, const float *__restrict__ im2,
+// neighbouring tiles share stay in one L2.  A tile is 64 E x 4 PX pixels: a lane owns E horizontally adjacent pixels (x = 64 E tx +
+// E lane ...), wavefront wv takes rows wv, wv+4, ... (PX of them) of the tile.  L1 = false: out_ is the warped image; L1 = true:
+// the fused warp + L1, out_ its two doubles.  The three instances in use:
+//   <false, 1, 4>, <true, 1, 4>  64 x 16 tiles, one pixel per lane, every load a dword;
+//   <true, 2, 2>                 even widths, fused warp + L1: 128 x 8 tiles, the streamed operands (flow, target, mask) arrive as
+//                                aligned 8-byte loads -- less addresser work than two dword loads -- the taps stay dword gathers.
+//                                217 -> 210 us on 64 frames of 480x854, bit-identical; the plain warp (which also streams its
+//                                output) is slower this way on wide images (265 vs 233 us) and keeps one pixel per lane.
+template <bool L1, int E, int PX>
+__global__ void __launch_bounds__(256) warp_tile_kernel(const float *__restrict__ im1, const float *__restrict__ im2,
                                                         const float *__restrict__ flow, const float *__restrict__ occ,
                                                         void *__restrict__ out_, int B, int H, int W, WarpGeom gm,
                                                         int tiles_x, int tiles_y) {
@@ -379,102 +332,36 @@ __global__ void __launch_bounds__(256) warp_rows_kernel(const float *__restrict_
     const int t0 = (int)((long)ntiles * xcd / 8), t1 = (int)((long)ntiles * (xcd + 1) / 8);
     const int per = t1 - t0, R = B * per;
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    double s = 0, so = 0;
+    double s[2] = {0, 0};                                       // sum |im1 - warped| occ, sum occ
     for (int r = j; r < R; r += Q) {
         const int b = r / per, t = t0 + (r - b * per);
         const int ty = t / tiles_x, tx = t - ty * tiles_x;
         const float *fl = flow + (long)b * 2 * HW, *src = im2 + (long)b * 3 * HW;
-        const int x = tx * TILE_W + lane;
-        const int xc = min(x, W - 1);
-        Tap4 tp[PX];
+        const int x = tx * (64 * E) + E * lane;                 // pixels x .. x + E - 1
+        const int xc = min(x, W - E);                           // E = 2: W is even, the pair is inside or outside as a whole
+        Tap4 tp[PX][E];
         int g[PX];
         bool ok[PX];
 #pragma unroll
         for (int k = 0; k < PX; ++k) {
             const int y = ty * (4 * PX) + wv + 4 * k;
-            ok[k] = x < W && y < H;
+            ok[k] = x + E - 1 < W && y < H;
             const int yc = min(y, H - 1);
             g[k] = yc * W + xc;
-            tp[k] = border_tap(xc, yc, fl[g[k]], fl[HW + g[k]], gm, W, H);
+            float fx[E], fy[E];
+            stream_load<E>(fl + g[k], fx);
+            stream_load<E>(fl + HW + g[k], fy);
+#pragma unroll
+            for (int e = 0; e < E; ++e) tp[k][e] = border_tap(xc + e, yc, fx[e], fy[e], gm, W, H);
         }
-        float v[3][PX];
+        float v[3][PX][E];
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
             const float *pl = src + c * HW;
-#pragma unroll
-            for (int k = 0; k < PX; ++k) {
-                const float *q = pl + tp[k].off;
-                v[c][k] = blend(v2f{q[0], q[1]}, v2f{q[W], q[W + 1]}, tp[k]);
-            }
-        }
-        if (L1) {
-            const float *tgt = im1 + (long)b * 3 * HW;
-            const float *oc = occ ? occ + (long)b * HW : nullptr;
-#pragma unroll
-            for (int k = 0; k < PX; ++k) {
-                float acc = 0.f;
-#pragma unroll
-                for (int c = 0; c < 3; ++c) acc += fabsf(tgt[c * HW + g[k]] - v[c][k]);
-                const float o = oc ? oc[g[k]] : 1.f;
-                if (ok[k]) {
-                    s += (double)(acc * o);
-                    so += (double)o;
-                }
-            }
-        } else {
-            float *ob = (float *)out_ + (long)b * 3 * HW;
 #pragma unroll
             for (int k = 0; k < PX; ++k)
-                if (ok[k])
 #pragma unroll
-                    for (int c = 0; c < 3; ++c) ob[c * HW + g[k]] = v[c][k];
-        }
-    }
-    if (L1) block_add2(s, so, (double *)out_);
-}
-
-// Even widths, fused warp + L1: a lane owns TWO horizontally adjacent pixels (128 x 8 tiles, 2 rows per thread): the streamed
-// operands (flow, target, mask) arrive as aligned 8-byte loads -- less addresser work than two dword loads -- the taps stay
-// dword gathers.  217 -> 210 us on 64 frames of 480x854, bit-identical; the plain warp (which also streams its output) is
-// slower this way on wide images (265 vs 233 us) and keeps one pixel per lane.
-template <bool L1>
-__global__ void __launch_bounds__(256) warp_rows2_kernel(const float *__restrict__ im1, const float *__restrict__ im2,
-                                                         const float *__restrict__ flow, const float *__restrict__ occ,
-                                                         void *__restrict__ out_, int B, int H, int W, WarpGeom gm,
-                                                         int tiles_x, int tiles_y) {
-    const int HW = H * W;
-    const int xcd = blockIdx.x & 7, j = blockIdx.x >> 3, Q = gridDim.x >> 3;
-    const int ntiles = tiles_x * tiles_y;
-    const int t0 = (int)((long)ntiles * xcd / 8), t1 = (int)((long)ntiles * (xcd + 1) / 8);
-    const int per = t1 - t0, R = B * per;
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    double s = 0, so = 0;
-    for (int r = j; r < R; r += Q) {
-        const int b = r / per, t = t0 + (r - b * per);
-        const int ty = t / tiles_x, tx = t - ty * tiles_x;
-        const float *fl = flow + (long)b * 2 * HW, *src = im2 + (long)b * 3 * HW;
-        const int x = tx * 128 + 2 * lane;                          // pixels x, x + 1
-        Tap4 tp[2][2];
-        int g[2];
-        bool ok[2][2];
-#pragma unroll
-        for (int k = 0; k < 2; ++k) {
-            const int y = ty * 8 + wv + 4 * k;
-            const int yc = min(y, H - 1), xc = min(x, W - 2);       // W is even here: (x, x+1) both inside or both outside
-            g[k] = yc * W + xc;
-            ok[k][0] = ok[k][1] = x + 1 < W && y < H;
-            const v2f fx = *reinterpret_cast<const v2f *>(fl + g[k]), fy = *reinterpret_cast<const v2f *>(fl + HW + g[k]);
-            tp[k][0] = border_tap(xc, yc, fx.x, fy.x, gm, W, H);
-            tp[k][1] = border_tap(xc + 1, yc, fx.y, fy.y, gm, W, H);
-        }
-        float v[3][2][2];
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            const float *pl = src + c * HW;
-#pragma unroll
-            for (int k = 0; k < 2; ++k)
-#pragma unroll
-                for (int e = 0; e < 2; ++e) {
+                for (int e = 0; e < E; ++e) {
                     const float *q = pl + tp[k][e].off;
                     v[c][k][e] = blend(v2f{q[0], q[1]}, v2f{q[W], q[W + 1]}, tp[k][e]);
                 }
@@ -483,33 +370,36 @@ __global__ void __launch_bounds__(256) warp_rows2_kernel(const float *__restrict
             const float *tgt = im1 + (long)b * 3 * HW;
             const float *oc = occ ? occ + (long)b * HW : nullptr;
 #pragma unroll
-            for (int k = 0; k < 2; ++k) {
-                v2f tg[3];
+            for (int k = 0; k < PX; ++k) {
+                float tg[3][E], o[E];
 #pragma unroll
-                for (int c = 0; c < 3; ++c) tg[c] = *reinterpret_cast<const v2f *>(tgt + c * HW + g[k]);
-                v2f o = {1.f, 1.f};
-                if (oc) o = *reinterpret_cast<const v2f *>(oc + g[k]);
+                for (int c = 0; c < 3; ++c) stream_load<E>(tgt + c * HW + g[k], tg[c]);
 #pragma unroll
-                for (int e = 0; e < 2; ++e) {
+                for (int e = 0; e < E; ++e) o[e] = 1.f;
+                if (oc) stream_load<E>(oc + g[k], o);
+#pragma unroll
+                for (int e = 0; e < E; ++e) {
                     float acc = 0.f;
 #pragma unroll
                     for (int c = 0; c < 3; ++c) acc += fabsf(tg[c][e] - v[c][k][e]);
-                    if (ok[k][e]) {
-                        s += (double)(acc * o[e]);
-                        so += (double)o[e];
+                    if (ok[k]) {
+                        s[0] += (double)(acc * o[e]);
+                        s[1] += (double)o[e];
                     }
                 }
             }
         } else {
             float *ob = (float *)out_ + (long)b * 3 * HW;
 #pragma unroll
-            for (int k = 0; k < 2; ++k)
-                if (ok[k][0])
+            for (int k = 0; k < PX; ++k)
+                if (ok[k])
 #pragma unroll
-                    for (int c = 0; c < 3; ++c) *reinterpret_cast<v2f *>(ob + c * HW + g[k]) = v2f{v[c][k][0], v[c][k][1]};
+                    for (int c = 0; c < 3; ++c)
+#pragma unroll
+                        for (int e = 0; e < E; ++e) ob[c * HW + g[k] + e] = v[c][k][e];
         }
     }
-    if (L1) block_add2(s, so, (double *)out_);
+    if (L1) block_add(s, (double *)out_);
 }
 
 // tile kernels for RGB / border calls; pad_mode | RCF_WARP_PER_PIXEL (a per-call choice: tests) keeps the per-pixel kernels, which
@@ -534,16 +424,17 @@ __global__ void __launch_bounds__(256) photometric_kernel(const float *__restric
     const float C1 = 0.01f * 0.01f, C2 = 0.03f * 0.03f;
     const int k = 2 * md + 1;
     const float inv = 1.f / (float)(k * k);
-    double s1 = 0, so = 0, ss = 0, dummy = 0;
+    double s[3] = {0, 0, 0};
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += step) {
-        const long b = i / HW, p = i - b * HW;
-        const int py = (int)(p / W), px = (int)(p - (long)py * W);
+        const PixelIdx ix = pixel_index(i, HW, W);
+        const long b = ix.b, p = ix.p;
+        const int py = ix.py, px = ix.px;
         const float o = occ[i];
-        so += (double)o;
+        s[1] += (double)o;
         const bool interior = py >= md && py < H - md && px >= md && px < W - md;
         for (int c = 0; c < C; ++c) {
             const float *a = im + (b * C + c) * HW, *r = rec + (b * C + c) * HW;
-            s1 += (double)(fabsf(a[p] - r[p]) * o);
+            s[0] += (double)(fabsf(a[p] - r[p]) * o);
             if (interior) {
                 float sx = 0, sy = 0, sxx = 0, syy = 0, sxy = 0;
                 for (int dy = -md; dy <= md; ++dy)
@@ -557,12 +448,11 @@ __global__ void __launch_bounds__(256) photometric_kernel(const float *__restric
                 const float vx = sxx * inv - mx * mx, vy = syy * inv - my * my, cxy = sxy * inv - mx * my;
                 const float n = (2.f * mx * my + C1) * (2.f * cxy + C2);
                 const float d = (mx * mx + my * my + C1) * (vx + vy + C2);
-                ss += (double)fminf(fmaxf((1.f - n / d) * 0.5f, 0.f), 1.f);
+                s[2] += (double)fminf(fmaxf((1.f - n / d) * 0.5f, 0.f), 1.f);
             }
         }
     }
-    block_add2(s1, so, sums);
-    block_add2(ss, dummy, sums + 2);
+    block_add(s, sums);
 }
 
 __global__ void photometric_final_kernel(const double *__restrict__ sums, float *__restrict__ out, float w_l1,
@@ -573,28 +463,42 @@ __global__ void photometric_final_kernel(const double *__restrict__ sums, float 
     out[0] = (float)(loss / (sums[1] / n_occ));
 }
 
+// what the warp and the fused warp + L1 entries check alike; takes RCF_WARP_PER_PIXEL off pad_mode
+inline bool warp_args_ok(bool pointers, int B, int C, int H, int W, int &pad_mode, bool &per_pixel) {
+    per_pixel = pad_mode & RCF_WARP_PER_PIXEL;
+    pad_mode &= ~RCF_WARP_PER_PIXEL;
+    if (!pointers || B <= 0 || C <= 0 || H < 2 || W < 2 || (pad_mode != 0 && pad_mode != 1)) return false;
+    return (long)H * W < (1L << 30);                            // the kernels hold H * W in an int
+}
+
+// the tile kernel over 64 E x 4 PX tiles with Q workgroups per XCD: one per `share` of the R tiles an XCD walks, 1 <= Q <= cap
+template <bool L1, int E, int PX>
+int launch_warp_tiles(const float *im1, const float *im2, const float *flow, const float *occ, void *out, int B, int H, int W,
+                      int share, int cap, hipStream_t st) {
+    const int tx = rcf_cdiv(W, 64 * E), ty = rcf_cdiv(H, 4 * PX);
+    const long R = (long)B * rcf_cdiv((long)tx * ty, 8);
+    const int Q = (int)(R < share ? 1 : (R / share < cap ? R / share : cap));
+    hipLaunchKernelGGL((warp_tile_kernel<L1, E, PX>), dim3((unsigned)(8 * Q)), dim3(256), 0, st, im1, im2, flow, occ, out, B, H, W,
+                       warp_geom(H, W), tx, ty);
+    RCF_LAUNCH_CHECK();
+    return 0;
+}
+
+inline int band_runs(int H, int W) { return rcf_cdiv((long)((H + 7) / 8) * W, 512); }      // 512-pixel runs per band
+
 }  // namespace
 
 extern "C" int rcf_flow_warp_f32(const float *x, const float *flow, float *out, int B, int C, int H, int W,
                                  int pad_mode, void *stream) {
-    const bool per_pixel = pad_mode & RCF_WARP_PER_PIXEL;
-    pad_mode &= ~RCF_WARP_PER_PIXEL;
-    if (!x || !flow || !out || B <= 0 || C <= 0 || H < 2 || W < 2 || (pad_mode != 0 && pad_mode != 1)) return RCF_EINVAL;
-    if ((long)H * W >= (1L << 30)) return RCF_EINVAL;
-    if (!per_pixel && warp_tile_applies(C, H, W, pad_mode) && W >= 256) {     // narrow images: the flat 512-pixel runs fill the lanes better
-        const int tx = rcf_cdiv(W, TILE_W), ty = rcf_cdiv(H, 16);
-        const long R = (long)B * rcf_cdiv((long)tx * ty, 8);
-        const int Q = (int)(R < 1024 ? R : 1024);               // up to 8192 workgroups, each walking its share of the tiles
-        hipLaunchKernelGGL((warp_rows_kernel<false, 4>), dim3((unsigned)(8 * Q)), dim3(256), 0, rcf_stream(stream),
-                           (const float *)nullptr, x, flow, (const float *)nullptr, (void *)out, B, H, W, warp_geom(H, W), tx,
-                           ty);
-        RCF_LAUNCH_CHECK();
-        return 0;
-    }
-    const int runs = rcf_cdiv((long)((H + 7) / 8) * W, 512);          // 512-pixel runs per band
+    bool per_pixel;
+    if (!warp_args_ok(x && flow && out, B, C, H, W, pad_mode, per_pixel)) return RCF_EINVAL;
+    if (!per_pixel && warp_tile_applies(C, H, W, pad_mode) && W >= 256)       // narrow images: the flat 512-pixel runs fill the lanes better
+        // up to 8192 workgroups, each walking its share of the tiles
+        return launch_warp_tiles<false, 1, 4>(nullptr, x, flow, nullptr, out, B, H, W, 1, 1024, rcf_stream(stream));
+    const int runs = band_runs(H, W);
     if ((long)8 * B * runs >= (1L << 31)) return RCF_EINVAL;
-    hipLaunchKernelGGL(flow_warp_kernel, dim3((unsigned)(8 * B * runs)), dim3(256), 0, rcf_stream(stream), x, flow, out, B,
-                       C, H, W, pad_mode, runs);
+    hipLaunchKernelGGL(flow_warp_kernel, dim3((unsigned)(8 * B * runs)), dim3(256), 0, rcf_stream(stream), x, flow, out, B, C, H, W,
+                       pad_mode, runs);
     RCF_LAUNCH_CHECK();
     return 0;
 }
@@ -633,30 +537,23 @@ extern "C" int rcf_occu_mask_bidirection_f32(const float *flow12, const float *f
 
 extern "C" int rcf_warp_l1_residual_f32(const float *im1, const float *im2, const float *flow, const float *occ,
                                         double *out, int B, int C, int H, int W, int pad_mode, void *stream) {
-    const bool per_pixel = pad_mode & RCF_WARP_PER_PIXEL;
-    pad_mode &= ~RCF_WARP_PER_PIXEL;
-    if (!im1 || !im2 || !flow || !out || B <= 0 || C <= 0 || H < 2 || W < 2 || (pad_mode != 0 && pad_mode != 1)) return RCF_EINVAL;
-    if ((long)H * W >= (1L << 30)) return RCF_EINVAL;           // the kernels hold H * W in an int
+    bool per_pixel;
+    if (!warp_args_ok(im1 && im2 && flow && out, B, C, H, W, pad_mode, per_pixel)) return RCF_EINVAL;
     hipStream_t st = rcf_stream(stream);
     hipError_t e = hipMemsetAsync(out, 0, 2 * sizeof(double), st);
     if (e != hipSuccess) return (int)e;
     if (!per_pixel && warp_tile_applies(C, H, W, pad_mode)) {
-        const bool two = W % 2 == 0;                            // two pixels per lane, 8-byte stream loads
-        const int tx = rcf_cdiv(W, two ? 128 : TILE_W), ty = rcf_cdiv(H, two ? 8 : 16);
-        const long R = (long)B * rcf_cdiv((long)tx * ty, 8);
         // 4096 workgroups at most, and at least four tiles each: every workgroup ends in two fp64 atomics on one address
-        const int Q = (int)(R < 4 ? 1 : (R / 4 < 512 ? R / 4 : 512));       // measured 64 / 128 / 256 / 512: 245 / 234 / 231 / 226 us
-        hipLaunchKernelGGL((two ? warp_rows2_kernel<true> : warp_rows_kernel<true, 4>), dim3((unsigned)(8 * Q)), dim3(256), 0, st, im1, im2, flow, occ,
-                           (void *)out, B, H, W, warp_geom(H, W), tx, ty);
-        RCF_LAUNCH_CHECK();
-        return 0;
+        // (measured 64 / 128 / 256 / 512 per XCD: 245 / 234 / 231 / 226 us).  Even widths: two pixels per lane, 8-byte stream loads
+        return W % 2 == 0 ? launch_warp_tiles<true, 2, 2>(im1, im2, flow, occ, out, B, H, W, 4, 512, st)
+                          : launch_warp_tiles<true, 1, 4>(im1, im2, flow, occ, out, B, H, W, 4, 512, st);
     }
     // 8 bands x 256 workgroups (2048 in total: each ends in two fp64 atomics), fewer when there is less work
-    const int runs = rcf_cdiv((long)((H + 7) / 8) * W, 512);          // 512-pixel runs per band
+    const int runs = band_runs(H, W);
     const long R = (long)B * runs;
     const int Q = (int)(R < 256 ? R : 256);
-    hipLaunchKernelGGL(warp_l1_kernel, dim3((unsigned)(8 * Q)), dim3(256), 0, st, im1, im2, flow, occ, out, B, C, H, W,
-                       pad_mode, runs);
+    hipLaunchKernelGGL(warp_l1_kernel, dim3((unsigned)(8 * Q)), dim3(256), 0, st, im1, im2, flow, occ, out, B, C, H, W, pad_mode,
+                       runs);
     RCF_LAUNCH_CHECK();
     return 0;
 }
