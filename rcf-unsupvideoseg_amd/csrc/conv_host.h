@@ -33,7 +33,7 @@ static inline int region_pixels(const rcf_conv_region *r, int H, int W) {       
     return r->band > 0 ? 2 * r->band * r->w + 2 * r->band * (r->h - 2 * r->band) : r->h * r->w;
 }
 
-// the region fields of a weight-gradient launch (WgradParams of either file); the caller checked region_ok over Ho x Wo
+// the region fields of a weight-gradient launch (WgradParamsT of wgrad_cols.h); the caller checked region_ok over Ho x Wo
 template <class P>
 static inline void fill_region(P &p, const rcf_conv_region *r, int N, int H, int W) {
     p.ry0 = r ? r->y0 : 0; p.rx0 = r ? r->x0 : 0; p.rh = r ? r->h : H; p.rw = r ? r->w : W;
@@ -97,7 +97,7 @@ static inline size_t wgrad_workspace_bytes(int splitk, const rcf_conv_shape *s) 
     return splitk <= 1 ? 0 : (size_t)splitk * s->Cout * s->R * s->S * s->Cin * sizeof(float);
 }
 
-// the launch parameters both weight gradients fill the same way (P = the file's WgradParams; X, DY and its own fields: the caller)
+// the launch parameters both weight gradients fill the same way (P = a WgradParamsT of wgrad_cols.h; X, DY and the ranges: the caller)
 template <class P, class PL>
 static inline void fill_wgrad(P &p, const PL &pl, const rcf_conv_shape *s, const rcf_conv_region *r, int beta, float *dw, void *workspace) {
     p.OUT = pl.splitk > 1 ? (float *)workspace : dw;
@@ -109,4 +109,5 @@ static inline void fill_wgrad(P &p, const PL &pl, const rcf_conv_shape *s, const
     p.split_stride = (long)s->Cout * s->R * s->S * s->Cin; p.beta = beta;
     p.xcd_map = (s->flags & RCF_CONV_NO_WGRAD_XCD) ? 0 : 1;
     p.cblocks = pl.cblocks;
+    p.Ktot = s->R * s->S * s->Cin;
 }

@@ -721,34 +721,8 @@ __global__ void __launch_bounds__(256) weight_bf16_kernel(const float *__restric
 }
 
 // ------------------------------------------------------------------------------------------- weight gradient
-struct WgradParams {
-    const bf16_t *X, *DY;
-    float *OUT;
-    int Cout, Cin, R, S;
-    int H, W, Ho, Wo, stride, pad, dil;
-    int x_pitch, dy_pitch;
-    long M;            // N * rr
-    long chunk;        // pixels per K-split (multiple of 32)
-    int itiles, jtiles;
-    long split_stride; // Cout*R*S*Cin
-    int beta;          // only honoured when gridDim.z == 1
-    int ry0, rx0, rh, rw, rband, rr;
-    int Ktot;          // R*S*Cin: the GEMM columns are (tap, input channel) pairs
-    int sched;         // LDS-DMA kernel: 1 = pieces interleaved with the MFMAs (default), 0 = ahead of them (A/B reference)
-    int xcd_map;       // rcf_wgrad_item mode (1 = an XCD's workgroups share their pixels)
-    int cblocks;       // rcf_wgrad_tile_ij (> 0: column tiles per tap, tiles numbered channel-block-major)
-};
-
-// byte offset `off` if ok == 1, an out-of-range offset (the load returns zeros) if ok == 0 -- arithmetic, so that a
-// K-step's loads stay in one basic block
-__device__ __forceinline__ unsigned oob_unless(unsigned off, int ok) { return (off & ~OOB) | ((unsigned)(ok - 1) & OOB); }
-
-typedef short s16x4 __attribute__((__vector_size__(4 * sizeof(short))));
-__device__ __forceinline__ u32x2 lds_tr16(const char *p) {
-    const s16x4 v = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-        (__attribute__((address_space(3))) s16x4 *)(__attribute__((address_space(3))) char *)p);
-    return __builtin_bit_cast(u32x2, v);
-}
+#include "wgrad_cols.h"
+using WgradParams = WgradParamsT<bf16_t>;
 
 // dw[co][rs][c] = sum_m dy[m][co] * x[src(m, rs)][c]: rows i = co (64 MR), cols j = (rs, c) (64 NR), K = pixels (32 per
 // step).  The taps are GEMM COLUMNS (j = rs * Cin + c, the weight's own memory order), not grid rows: a tile of a
@@ -762,69 +736,33 @@ __global__ void __launch_bounds__(256, 2) wgrad_bf16_kernel(WgradParams p) {
     constexpr int BM = 64 * MR, BN = 64 * NR, BK = 32;
     constexpr int QA = BM / 8, PAS = 256 / QA, NAP = BK / PAS;   // dy loader: 16-byte chunks per pixel, pixels per pass, passes
     constexpr int QB = BN / 8, PBS = 256 / QB, NBP = BK / PBS;   // x loader
-    // row pitch = channels * 2 + 64 bytes: the 4 pixel rows a 16-lane group reads are 64 B apart in bank space and the
-    // second group of a 32-lane half (channels + 16 = + 32 B) falls into the gaps: 256 distinct bytes per LDS cycle
-    constexpr int PIA = BM * 2 + 64, PIB = BN * 2 + 64;
+    constexpr int PIA = BM * 2 + 64, PIB = BN * 2 + 64;          // padded row pitch (wgrad_cols.h wgrad_frag_padded)
     constexpr int PLA = BK * PIA, PLB = BK * PIB, STAGE = PLA + PLB;
     __shared__ __attribute__((aligned(16))) char smem[2 * STAGE];
 
-    int tile, split;
-    rcf_wgrad_item(p.xcd_map, tile, split);
-    int tile_i, tile_j;
-    rcf_wgrad_tile_ij(tile, p.itiles, p.jtiles, p.cblocks, tile_i, tile_j);
-    const int i0 = tile_i * BM, j0 = tile_j * BN;
-    const long kbeg = (long)split * p.chunk;
-    const long kend = min(p.M, kbeg + p.chunk);
-    const int klen = (int)(kend - kbeg);
-
+    const WgradItem it = wgrad_item<BM, BN>(p);
+    const int i0 = it.i0, j0 = it.j0, klen = it.klen;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wm = wave >> 1, wn = wave & 1;
-    const int HoWo = p.rr;
-    const int n_first = (int)(kbeg / HoWo);
-    // whole tensors: the contributing pixels are the rows of dy in order, no walk needed
-    const __amdgpu_buffer_rsrc_t rsA = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<bf16_t *>(p.DY + (REGION ? (long)n_first * p.Ho * p.Wo : kbeg) * p.dy_pitch), 0, (int)OOB, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsB = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<bf16_t *>(p.X + (long)n_first * p.H * p.W * p.x_pitch), 0, (int)OOB, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsA = wgrad_dy_rsrc<REGION>(p, it), rsB = wgrad_x_rsrc(p, it);
 
     const int qa = tid % QA, pa0 = tid / QA;
     const int qb = tid % QB, pb0 = tid / QB;
-    const int cha = i0 + 8 * qa, jc = j0 + 8 * qb;          // this thread's dy channels / GEMM columns (one tap: Cin % 8 == 0)
-    const int rs = jc / p.Cin, chb = jc - rs * p.Cin;
-    const int r = rs / p.S, s = rs - r * p.S;
-    const bool acta = cha < p.Cout, actb = jc < p.Ktot;
-    // pixel walkers (image-relative to n_first), advanced by BK per K-step
-    int an[NAP], ay[NAP], ax[NAP], apix[NAP];
-    int bn[NBP], by[NBP], bx[NBP], bpix[NBP];
-    auto init_px = [&](long m, int &n, int &y, int &x, int &pix) {
-        n = (int)(m / HoWo);
-        pix = (int)(m - (long)n * HoWo);
-        if (REGION) region_yx(pix, p.ry0, p.rx0, p.rh, p.rw, p.rband, y, x);
-        else { y = pix / p.Wo; x = pix - y * p.Wo; }
-        n -= n_first;
-    };
+    const int cha = i0 + 8 * qa;                                 // this thread's dy channels
+    const WgradCol col = wgrad_col<false>(p, j0, j0 + 8 * qb);   // ... and GEMM columns (one tap: Cin % 8 == 0)
+    const bool acta = cha < p.Cout;
+    // one pixel walker per loader pass, advanced by BK per K-step (whole tensors read dy in order: no walk)
+    WgradWalk<REGION, BK> wa[NAP], wb[NBP];
     if (REGION) {
 #pragma unroll
-        for (int j = 0; j < NAP; ++j) init_px(kbeg + pa0 + PAS * j, an[j], ay[j], ax[j], apix[j]);
+        for (int j = 0; j < NAP; ++j) wa[j].init(p, it, pa0 + PAS * j);
     }
 #pragma unroll
-    for (int j = 0; j < NBP; ++j) init_px(kbeg + pb0 + PBS * j, bn[j], by[j], bx[j], bpix[j]);
+    for (int j = 0; j < NBP; ++j) wb[j].init(p, it, pb0 + PBS * j);
     const bool incr = !REGION && p.Wo >= BK;
-    auto advance = [&](int &n, int &y, int &x, int &pix) {
-        if (incr) {                              // Wo >= BK: at most one row wrap per K-step
-            x += BK;
-            const bool wx = x >= p.Wo;
-            x -= wx ? p.Wo : 0;
-            y += wx ? 1 : 0;
-            const bool wy = y == p.Ho;
-            y = wy ? 0 : y;
-            n += wy ? 1 : 0;
-        } else {
-            pix += BK;
-            while (pix >= HoWo) { pix -= HoWo; ++n; }
-            if (REGION) region_yx(pix, p.ry0, p.rx0, p.rh, p.rw, p.rband, y, x);
-            else { y = pix / p.Wo; x = pix - y * p.Wo; }
-        }
+    auto advance = [&](WgradWalk<REGION, BK> &w) {
+        if (incr) w.advance_rows(p);
+        else w.advance_div(p);
     };
 
     u32x4 ra[NAP], rb[NBP];
@@ -835,8 +773,8 @@ __global__ void __launch_bounds__(256, 2) wgrad_bf16_kernel(WgradParams p) {
             const bool v = acta && mk < klen;
             unsigned bo;
             if (REGION) {
-                bo = v ? (unsigned)(((an[j] * p.Ho + ay[j]) * p.Wo + ax[j]) * p.dy_pitch + cha) * 2u : OOB;
-                advance(an[j], ay[j], ax[j], apix[j]);
+                bo = v ? (unsigned)(((wa[j].pn * p.Ho + wa[j].py) * p.Wo + wa[j].px) * p.dy_pitch + cha) * 2u : OOB;
+                advance(wa[j]);
             } else {
                 bo = v ? (unsigned)(mk * p.dy_pitch + cha) * 2u : OOB;
             }
@@ -845,12 +783,12 @@ __global__ void __launch_bounds__(256, 2) wgrad_bf16_kernel(WgradParams p) {
 #pragma unroll
         for (int j = 0; j < NBP; ++j) {
             const int mk = kt * BK + pb0 + PBS * j;
-            const int sy = by[j] * p.stride - p.pad + r * p.dil;
-            const int sx = bx[j] * p.stride - p.pad + s * p.dil;
-            const bool v = actb && mk < klen && (unsigned)sy < (unsigned)p.H && (unsigned)sx < (unsigned)p.W;
-            const unsigned bo = v ? (unsigned)(((bn[j] * p.H + sy) * p.W + sx) * p.x_pitch + chb) * 2u : OOB;
+            const int sy = wb[j].py * p.stride - p.pad + col.r * p.dil;
+            const int sx = wb[j].px * p.stride - p.pad + col.s * p.dil;
+            const bool v = col.act && mk < klen && (unsigned)sy < (unsigned)p.H && (unsigned)sx < (unsigned)p.W;
+            const unsigned bo = v ? (unsigned)(((wb[j].pn * p.H + sy) * p.W + sx) * p.x_pitch + col.ch) * 2u : OOB;
             rb[j] = __builtin_amdgcn_raw_buffer_load_b128(rsB, (int)bo, 0, 0);
-            advance(bn[j], by[j], bx[j], bpix[j]);
+            advance(wb[j]);
         }
     };
     auto store_tile = [&](int buf) {
@@ -862,19 +800,10 @@ __global__ void __launch_bounds__(256, 2) wgrad_bf16_kernel(WgradParams p) {
     };
 
     f32x16 acc[MR][NR];
-#pragma unroll
-    for (int mr = 0; mr < MR; ++mr)
-#pragma unroll
-        for (int nr = 0; nr < NR; ++nr)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) acc[mr][nr][e] = 0.f;
+    wgrad_clear(acc);
 
     const int arow0 = wm * 32 * MR, brow0 = wn * 32 * NR;
-    // fragment addressing (see igemm_wgrad_h2t_kernel): 16-lane group gi serves tile rows 16 (gi & 1) .. +15 and the k
-    // half gi >> 1; lane q of the group points at pixel row 8 (gi >> 1) + q / 4 (+ 4 for the second read), channels 4 (q % 4)
-    const int gi = lane >> 4, q16 = lane & 15;
-    const int fa = (8 * (gi >> 1) + (q16 >> 2)) * PIA + (arow0 + 16 * (gi & 1) + 4 * (q16 & 3)) * 2;
-    const int fb = (8 * (gi >> 1) + (q16 >> 2)) * PIB + (brow0 + 16 * (gi & 1) + 4 * (q16 & 3)) * 2;
+    const int fa = wgrad_frag_padded(lane, arow0, PIA), fb = wgrad_frag_padded(lane, brow0, PIB);
     auto mma = [&](int buf) {
         const char *As = smem + buf * STAGE, *Bs = As + PLA;
 #pragma unroll
@@ -914,37 +843,8 @@ __global__ void __launch_bounds__(256, 2) wgrad_bf16_kernel(WgradParams p) {
     }
     mma((KT - 1) & 1);
 
-    float *out = p.OUT + (long)split * p.split_stride;
-    const int l31 = lane & 31, kh = lane >> 5;
-    if (i0 + 32 * MR * 2 <= p.Cout && j0 + 32 * NR * 2 <= p.Ktot && !(p.beta && gridDim.z == 1)) {
-        // the tile lies inside the weight tensor and is a split-K partial (or overwrites): store, nothing to test
-#pragma unroll
-        for (int mr = 0; mr < MR; ++mr)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) {
-                float *drow = out + (long)(i0 + arow0 + mr * 32 + 4 * kh + (e & 3) + 8 * (e >> 2)) * p.Ktot + j0 + brow0 + l31;
-#pragma unroll
-                for (int nr = 0; nr < NR; ++nr) drow[nr * 32] = acc[mr][nr][e];
-            }
-        return;
-    }
-#pragma unroll
-    for (int mr = 0; mr < MR; ++mr) {
-        const int rbase = i0 + arow0 + mr * 32 + 4 * kh;
-#pragma unroll
-        for (int e = 0; e < 16; ++e) {
-            const int co = rbase + (e & 3) + 8 * (e >> 2);
-            if (co >= p.Cout) continue;
-            float *drow = out + (long)co * p.Ktot + j0 + brow0 + l31;
-#pragma unroll
-            for (int nr = 0; nr < NR; ++nr) {
-                if (j0 + brow0 + nr * 32 + l31 >= p.Ktot) continue;
-                float v = acc[mr][nr][e];
-                if (p.beta && gridDim.z == 1) v += drow[nr * 32];
-                drow[nr * 32] = v;
-            }
-        }
-    }
+    wgrad_store_tile<MR, NR, false>(acc, p.OUT + (long)it.split * p.split_stride, i0, j0, arow0, brow0, p.Cout, p.Ktot,
+                                    p.beta && gridDim.z == 1, 1.f, 1.f);
 }
 
 // one K-step of the LDS-DMA weight-gradient kernel: two 16-pixel substeps, fragments through the transposing reads.
@@ -978,235 +878,23 @@ __device__ __forceinline__ void wgrad_tr_step(const char *__restrict__ As, const
 }
 
 // The 128-row tiles again with LDS-DMA loads (buffer_load ... lds), three LDS stages and one barrier per K-step, like
-// conv_bf16_kernel<..., DMA>.  LDS image per operand: [channel group of 64][32 pixels][128 B] -- a DMA instruction (1 KB,
-// lane-linear) is 8 pixel rows of ONE channel group, so every thread serves ONE pixel (8 wave + lane / 8) in all of its
-// instructions: one pixel walk and one bounds test per K-step instead of one per load (the register-staged kernel spends
-// 9.5 VALU instructions per MFMA, mostly on that).  The 16-byte chunks of pixel row p are XOR-swizzled by
-// ((p >> 1) & 1) << 2 (source address and fragment address alike): the 4 rows x 4 chunks a 32-lane half reads through
-// ds_read_b64_tr_b16 cover all 16 chunk positions of the 256-byte bank space (SQ_LDS_BANK_CONFLICT = 0).
+// conv_bf16_kernel<..., DMA>: wgrad_cols.h wgrad_dma_body on one 16-bit plane, K-step 32, one MFMA pass.  Every thread serves ONE
+// pixel (8 wave + lane / 8) in all of its DMA instructions: one pixel walk and one bounds test per K-step instead of one per load
+// (the register-staged kernel spends 9.5 VALU instructions per MFMA, mostly on that).
 // ONETAP: Cin is a multiple of the tile width, so a tile's columns belong to one filter tap.
-// MR = 4 (rcf_conv_set_wgrad_big): 256 x 256 tile, one workgroup per CU (96 KB of LDS, 256 accumulator registers per wave).
-template <int NR, bool REGION, bool ONETAP, int MR = 2>
-__global__ void __launch_bounds__(256, MR == 2 ? 2 : 1) wgrad_bf16_dma_kernel(WgradParams p) {
-    constexpr int BM = 64 * MR, BN = 64 * NR, BK = 32;
-    constexpr int GA = BM / 64, GB = BN / 64;                  // channel groups = DMA instructions per wave and K-step
-    constexpr int GSZ = BK * 128;                              // bytes of one group: 32 pixels x 128 B
-    constexpr int PLA = GA * GSZ, PLB = GB * GSZ, STAGE = PLA + PLB;
-    __shared__ __attribute__((aligned(16))) char smem[3 * STAGE];
-
-    int tile, split;
-    rcf_wgrad_item(p.xcd_map, tile, split);
-    int tile_i, tile_j;
-    rcf_wgrad_tile_ij(tile, p.itiles, p.jtiles, p.cblocks, tile_i, tile_j);
-    const int i0 = tile_i * BM, j0 = tile_j * BN;
-    const long kbeg = (long)split * p.chunk;
-    const long kend = min(p.M, kbeg + p.chunk);
-    const int klen = (int)(kend - kbeg);
-
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wm = wave >> 1, wn = wave & 1;
-    const int HoWo = p.rr;
-    const int n_first = (int)(kbeg / HoWo);
-    const __amdgpu_buffer_rsrc_t rsA = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<bf16_t *>(p.DY + (REGION ? (long)n_first * p.Ho * p.Wo : kbeg) * p.dy_pitch), 0, (int)OOB, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsB = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<bf16_t *>(p.X + (long)n_first * p.H * p.W * p.x_pitch), 0, (int)OOB, 0x00020000);
-
-    // this thread's pixel row of the K-step and its chunk position inside a 128-byte group row
-    const int prow = 8 * wave + (lane >> 3), qpos = lane & 7;
-    const int qsrc = qpos ^ (((prow >> 1) & 1) << 2);          // source chunk of that position
-    int pn, py, px, ppix;                                      // the pixel walk (image index relative to n_first)
-    {
-        const long m = kbeg + prow;
-        pn = (int)(m / HoWo);
-        ppix = (int)(m - (long)pn * HoWo);
-        if (REGION) region_yx(ppix, p.ry0, p.rx0, p.rh, p.rw, p.rband, py, px);
-        else { py = ppix / p.Wo; px = ppix - py * p.Wo; }
-        pn -= n_first;
+struct WgradOp16 {
+    typedef bf16_t T;
+    static constexpr int BK = 32, PLANES = 1, PASSES = 2;      // (2 substeps of 16 pixels: 2 MFMAs per fragment pair and K-step)
+    static constexpr bool SCALED = false;
+    template <int MR, int NR, int PLA>
+    static __device__ __forceinline__ void mma(const char *S, const int (&fa)[MR], const int (&fb)[NR], f32x16 (&acc)[MR][NR]) {
+        wgrad_tr_step<MR, NR>(S, S + PLA, fa, fb, acc);
     }
-    const bool incr = !REGION && p.Wo >= BK;
-    int cha[GA], chb[GB], tr[GB], ts[GB];
-    bool acta[GA], actb[GB];
-#pragma unroll
-    for (int g = 0; g < GA; ++g) {
-        cha[g] = i0 + 64 * g + 8 * qsrc;
-        acta[g] = cha[g] < p.Cout;
-    }
-#pragma unroll
-    for (int g = 0; g < GB; ++g) {
-        const int jc = j0 + 64 * g + 8 * qsrc;                 // GEMM column = (tap, channel)
-        const int rs = (ONETAP ? j0 : jc) / p.Cin;
-        chb[g] = jc - rs * p.Cin;
-        tr[g] = rs / p.S;
-        ts[g] = rs - tr[g] * p.S;
-        actb[g] = jc < p.Ktot;
-    }
-    const int wb = __builtin_amdgcn_readfirstlane(wave) * 1024;    // 8 pixel rows x 128 B of each group
-    auto loads = [&](int kt, int stage) {                  // K-steps are issued in order: the walk advances by BK each time
-        char *As = smem + stage * STAGE + wb;
-        char *Bs = smem + stage * STAGE + PLA + wb;
-        const int mk = kt * BK + prow;
-        const bool inb = mk < klen;
-        const int dyoff = REGION ? ((pn * p.Ho + py) * p.Wo + px) * p.dy_pitch : mk * p.dy_pitch;
-#pragma unroll
-        for (int g = 0; g < GA; ++g) {
-            const unsigned bo = oob_unless((unsigned)(dyoff + cha[g]) * 2u, (int)inb & (int)acta[g]);
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsA, (__attribute__((address_space(3))) void *)(As + g * GSZ), 16, (int)bo, 0, 0, 0);
-        }
-        if constexpr (ONETAP) {
-            const int sy = py * p.stride - p.pad + tr[0] * p.dil, sx = px * p.stride - p.pad + ts[0] * p.dil;
-            const int v = (int)inb & (int)((unsigned)sy < (unsigned)p.H) & (int)((unsigned)sx < (unsigned)p.W);
-            const int xoff = ((pn * p.H + sy) * p.W + sx) * p.x_pitch;
-#pragma unroll
-            for (int g = 0; g < GB; ++g) {
-                const unsigned bo = oob_unless((unsigned)(xoff + chb[g]) * 2u, (int)v & (int)actb[g]);
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(rsB, (__attribute__((address_space(3))) void *)(Bs + g * GSZ), 16, (int)bo, 0, 0, 0);
-            }
-        } else {
-#pragma unroll
-            for (int g = 0; g < GB; ++g) {
-                const int sy = py * p.stride - p.pad + tr[g] * p.dil, sx = px * p.stride - p.pad + ts[g] * p.dil;
-                const int v = (int)inb & (int)actb[g] & (int)((unsigned)sy < (unsigned)p.H) & (int)((unsigned)sx < (unsigned)p.W);
-                const unsigned bo = oob_unless((unsigned)(((pn * p.H + sy) * p.W + sx) * p.x_pitch + chb[g]) * 2u, v);
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(rsB, (__attribute__((address_space(3))) void *)(Bs + g * GSZ), 16, (int)bo, 0, 0, 0);
-            }
-        }
-    };
-    auto advance_rows = [&]() {                  // Wo >= BK: at most one row wrap per K-step (no branches)
-        px += BK;
-        const bool wx = px >= p.Wo;
-        px -= wx ? p.Wo : 0;
-        py += wx ? 1 : 0;
-        const bool wy = py == p.Ho;
-        py = wy ? 0 : py;
-        pn += wy ? 1 : 0;
-    };
-    auto issue = [&](int kt, int stage) {
-        loads(kt, stage);
-        if (incr) {
-            advance_rows();
-        } else {
-            ppix += BK;
-            while (ppix >= HoWo) { ppix -= HoWo; ++pn; }
-            if (REGION) region_yx(ppix, p.ry0, p.rx0, p.rh, p.rw, p.rband, py, px);
-            else { py = ppix / p.Wo; px = ppix - py * p.Wo; }
-        }
-    };
-
-    f32x16 acc[MR][NR];
-#pragma unroll
-    for (int mr = 0; mr < MR; ++mr)
-#pragma unroll
-        for (int nr = 0; nr < NR; ++nr)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) acc[mr][nr][e] = 0.f;
-
-    const int arow0 = wm * 32 * MR, brow0 = wn * 32 * NR;
-    // fragment addressing: 16-lane group gi serves tile rows (channels) 16 (gi & 1) .. +15 and the k half gi >> 1; lane q of
-    // the group points at pixel row 8 (gi >> 1) + q / 4 (+ 4 for the second read), channels 4 (q % 4) .. + 3 of its 16
-    const int gi = lane >> 4, q16 = lane & 15;
-    const int fprow = 8 * (gi >> 1) + (q16 >> 2);
-    const int swz = ((fprow >> 1) & 1) << 2;                              // (+4, +16 j leave bit 1 of the pixel row alone)
-    const int cin = 16 * (gi & 1) + 4 * (q16 & 3);                         // channel inside a 32-channel tile
-    const int wi = (cin & 7) * 2;
-    int fa[MR], fb[NR];
-#pragma unroll
-    for (int mr = 0; mr < MR; ++mr) {
-        const int c = arow0 + mr * 32 + cin;
-        fa[mr] = (c >> 6) * GSZ + fprow * 128 + ((((c >> 3) & 7) ^ swz) << 4) + wi;
-    }
-#pragma unroll
-    for (int nr = 0; nr < NR; ++nr) {
-        const int c = brow0 + nr * 32 + cin;
-        fb[nr] = (c >> 6) * GSZ + fprow * 128 + ((((c >> 3) & 7) ^ swz) << 4) + wi;
-    }
-    auto mma = [&](int stage) {
-        const char *As = smem + stage * STAGE;
-        wgrad_tr_step<MR, NR>(As, As + PLA, fa, fb, acc);
-    };
-
-    constexpr int NLD = GA + GB;
-    const int KT = (klen + BK - 1) / BK;
-    issue(0, 0);
-    if (KT > 1) issue(1, 1);
-    if (KT > 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NLD) : "memory");
-    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    int st = 0, kt = 0;
-    if (incr && p.sched) {
-        // steady state as ONE basic block (conv_bf16_kernel<..., SCHED = 1>): fragment reads, then one LDS-DMA piece behind
-        // each of the first MFMAs
-        for (; kt + 2 < KT; ++kt) {
-            const int st2 = st >= 1 ? st - 1 : 2;         // (st + 2) % 3
-            mma(st);
-            loads(kt + 2, st2);
-            advance_rows();
-            if constexpr (MR == 4) {
-                // 256 x 256: the fragments of ONE k half at a time (64 registers for both would spill beside 256 accumulators)
-                __builtin_amdgcn_sched_group_barrier(0x100, 2 * (MR + NR), 0);
-#pragma unroll
-                for (int i = 0; i < NLD; ++i) {
-                    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                    __builtin_amdgcn_sched_group_barrier(0x010, 1, 0);
-                }
-                __builtin_amdgcn_sched_group_barrier(0x008, MR * NR - NLD, 0);
-                __builtin_amdgcn_sched_group_barrier(0x100, 2 * (MR + NR), 0);
-                __builtin_amdgcn_sched_group_barrier(0x008, MR * NR, 0);
-            } else {
-            __builtin_amdgcn_sched_group_barrier(0x100, 4 * (MR + NR), 0);
-#pragma unroll
-            for (int i = 0; i < NLD; ++i) {
-                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                __builtin_amdgcn_sched_group_barrier(0x010, 1, 0);
-            }
-            __builtin_amdgcn_sched_group_barrier(0x008, 2 * MR * NR - NLD, 0);
-            }
-            asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(NLD) : "memory");
-            __builtin_amdgcn_s_barrier();
-            st = st == 2 ? 0 : st + 1;
-        }
-    }
-    for (; kt < KT; ++kt) {
-        const int st2 = st >= 1 ? st - 1 : 2;
-        if (kt + 2 < KT) issue(kt + 2, st2);
-        mma(st);
-        if (kt + 2 < KT) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NLD) : "memory");
-        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        st = st == 2 ? 0 : st + 1;
-    }
-
-    float *out = p.OUT + (long)split * p.split_stride;
-    const int l31 = lane & 31, kh = lane >> 5;
-    if (i0 + 32 * MR * 2 <= p.Cout && j0 + 32 * NR * 2 <= p.Ktot && !(p.beta && gridDim.z == 1)) {
-        // the tile lies inside the weight tensor and is a split-K partial (or overwrites): store, nothing to test
-#pragma unroll
-        for (int mr = 0; mr < MR; ++mr)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) {
-                float *drow = out + (long)(i0 + arow0 + mr * 32 + 4 * kh + (e & 3) + 8 * (e >> 2)) * p.Ktot + j0 + brow0 + l31;
-#pragma unroll
-                for (int nr = 0; nr < NR; ++nr) drow[nr * 32] = acc[mr][nr][e];
-            }
-        return;
-    }
-#pragma unroll
-    for (int mr = 0; mr < MR; ++mr) {
-        const int rbase = i0 + arow0 + mr * 32 + 4 * kh;
-#pragma unroll
-        for (int e = 0; e < 16; ++e) {
-            const int co = rbase + (e & 3) + 8 * (e >> 2);
-            if (co >= p.Cout) continue;
-            float *drow = out + (long)co * p.Ktot + j0 + brow0 + l31;
-#pragma unroll
-            for (int nr = 0; nr < NR; ++nr) {
-                if (j0 + brow0 + nr * 32 + l31 >= p.Ktot) continue;
-                float v = acc[mr][nr][e];
-                if (p.beta && gridDim.z == 1) v += drow[nr * 32];
-                drow[nr * 32] = v;
-            }
-        }
-    }
+};
+template <int NR, bool REGION, bool ONETAP>
+__global__ void __launch_bounds__(256, 2) wgrad_bf16_dma_kernel(WgradParams p) {
+    __shared__ __attribute__((aligned(16))) char smem[3 * (2 + NR) * WgradOp16::BK * 128];
+    wgrad_dma_body<WgradOp16, NR, REGION, ONETAP>(p, smem);
 }
 
 // ------------------------------------------------------------------------------------------- host side (+ conv_host.h)
@@ -1527,8 +1215,6 @@ extern "C" int rcf_conv2d_wgrad_bf16(const void *x, const void *dy, float *dw, c
     WgradParams p{};
     p.X = (const bf16_t *)x; p.DY = (const bf16_t *)dy;
     fill_wgrad(p, pl, s, region, beta, dw, workspace);
-    p.Ktot = s->R * s->S * s->Cin;
-    p.sched = 1;
     const dim3 grid((unsigned)(pl.itiles * pl.jtiles), 1u, (unsigned)pl.splitk);
     const bool reg = region != nullptr;
 #define RCF_GO(...) hipLaunchKernelGGL((__VA_ARGS__), grid, dim3(256), 0, st, p)

@@ -519,8 +519,7 @@ __device__ __forceinline__ void mma_x3(const char *__restrict__ As, const char *
 }
 
 constexpr unsigned X3_OOB = 0x80000000u;      // byte offset beyond every descriptor's num_records: loads return 0
-// `off` if ok == 1, an out-of-range offset if ok == 0: arithmetic (a select on a load's address tends to become a branch)
-__device__ __forceinline__ unsigned x3_oob_unless(unsigned off, int ok) { return (off & ~X3_OOB) | ((unsigned)(ok - 1) & X3_OOB); }
+#include "wgrad_cols.h"                       // oob_unless, lds_tr16, and what the tap-column weight gradients share
 
 // The epilogue of the transposed-accumulator conv kernels (igemm_conv_x3_kernel, conv_h2d_kernel): a lane owns pixel lane&31 of
 // each row tile and, per register quad, output channels 8g + 4(lane>>5) .. +3 of each column tile -- 16-byte stores, the region walk
@@ -1269,23 +1268,7 @@ __global__ void __launch_bounds__(256) wprep_pairs_t_kernel(const rcf_wprep_entr
 #include "igemm_h2d.inc"
 
 // ------------------------------------------------------------------------------------------- wgrad
-struct WgradParams {
-    const float *X, *DY;
-    float *OUT;
-    int Cout, Cin, R, S;
-    int H, W, Ho, Wo, stride, pad, dil;
-    int x_pitch, dy_pitch;
-    long M;            // N*Ho*Wo
-    long chunk;        // pixels per K-split (multiple of BK)
-    int itiles, jtiles;
-    long split_stride; // Cout*R*S*Cin
-    int beta;          // only honoured when gridDim.z == 1
-    int ry0, rx0, rh, rw;   // split-bf16 kernel: contributing output pixels = this rectangle of every image (M = N*rr)
-    int rband, rr;          // frame thickness (0 = whole rectangle), pixels per image
-    const unsigned *amax_a, *amax_b;   // fp16-pair kernels: max |dy|, max |x| (raw fp32 bits, device scalars)
-    int xcd_map;       // igemm_wgrad_h2t_kernel: rcf_wgrad_item mode (1 = an XCD's workgroups share their pixels)
-    int cblocks;       // igemm_wgrad_h2t_kernel: rcf_wgrad_tile_ij (> 0: column tiles per tap, tiles numbered channel-block-major)
-};
+using WgradParams = WgradParamsT<float>;          // wgrad_cols.h (ry0 .. rr: the split-bf16 / fp16-pair kernels)
 
 // dw[co][rs][c] = sum_m dy[m][co] * x[src(m, rs)][c].  rows i = co, cols j = c, K = pixels.
 // SMALLC (Cin == 4, e.g. the zero-padded RGB stem): the taps become GEMM columns (j = rs*4 + c) instead of
@@ -1780,25 +1763,14 @@ __global__ void __launch_bounds__(256, 2) igemm_wgrad_x3_wide_kernel(WgradParams
 // The same 128 x 256 weight-gradient tile with the operands staged in their NATURAL order: LDS holds, per fp16 plane,
 // [16 pixels][channels] (a float4 = 4 channels of a pixel is split once and written with one ds_write_b64 per plane;
 // the global loads of a K-step are whole runs of 512 B / 1 KB per pixel), and the MFMA's k-contiguous fragments come out
-// of gfx950's transposing LDS read: ds_read_b64_tr_b16 gives lane c of a 16-lane group the 4 k-values of channel
-// c0 + c when lane p of the group points at row k0 + p/4, channels c0 + 4 (p%4) .. +3.  No register transposes, no
-// row permutation.  Row pitch = channels * 2 + 64 bytes: the 64-byte runs that a 32-lane half reads from 4 rows tile the
-// 256-byte bank space (a pitch of 32 mod 256 made neighbouring rows overlap by half: SQ_LDS_BANK_CONFLICT 33 % of the
-// LDS cycles).
-typedef short s16x4 __attribute__((__vector_size__(4 * sizeof(short))));
-__device__ __forceinline__ u32x2 lds_tr16(const char *p) {
-    const s16x4 v = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-        (__attribute__((address_space(3))) s16x4 *)(__attribute__((address_space(3))) char *)p);
-    return __builtin_bit_cast(u32x2, v);
-}
-
+// of gfx950's transposing LDS read (wgrad_cols.h: lds_tr16, wgrad_frag_padded and its row pitch).
 // NR = 4: 128 x 256 tile; NR = 2: 128 x 128 (operands too narrow for the wide tile).
 // The GEMM columns are (tap, input channel) pairs, j = rs * Cin + c -- the weight's own memory order -- and not grid rows:
 // a tile of a narrow layer (Cin = 64: 576 columns of a 3x3 filter) spans several taps, so dy is read once per 256 columns
 // instead of once per tap.  Cin % 64 == 0: each of a thread's 64-channel groups lies in ONE tap, which is block-uniform
 // (scalar registers).  ONETAP: Cin % BN == 0, the whole tile belongs to one tap.
 // REGION: only the pixels of p's rectangle / frame contribute (M = N * rr); the pixel walk divides.
-// MR = 4 (rcf_conv_set_wgrad_big): a 256 x 256 tile, ONE workgroup per CU -- 128 x 128 accumulators per wave (256 registers),
+// MR = 4 (plan_wgrad): a 256 x 256 tile, ONE workgroup per CU -- 128 x 128 accumulators per wave (256 registers),
 // 74 KB of LDS: a third fewer loads, splits, LDS writes and fragment reads per MFMA than the 128 x 256 tile.
 template <int NR, bool REGION, bool ONETAP, int MR = 2>
 __global__ void __launch_bounds__(256, MR == 2 ? 2 : 1) igemm_wgrad_h2t_kernel(WgradParams p) {
@@ -1808,24 +1780,13 @@ __global__ void __launch_bounds__(256, MR == 2 ? 2 : 1) igemm_wgrad_h2t_kernel(W
     constexpr int PLA = BK * PIA, PLB = BK * PIB, STAGE = 2 * (PLA + PLB);
     __shared__ __attribute__((aligned(16))) char smem[2 * STAGE];
 
-    int tile, split;
-    rcf_wgrad_item(p.xcd_map, tile, split);
-    int tile_i, tile_j;
-    rcf_wgrad_tile_ij(tile, p.itiles, p.jtiles, p.cblocks, tile_i, tile_j);
-    const int i0 = tile_i * BM, j0 = tile_j * BN;
-    const int Ktot = p.R * p.S * p.Cin;
-    const long kbeg = (long)split * p.chunk;
-    const long kend = min(p.M, kbeg + p.chunk);
-    const int klen = (int)(kend - kbeg);
-
+    const WgradItem it = wgrad_item<BM, BN>(p);
+    const int i0 = it.i0, j0 = it.j0, klen = it.klen;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wm = wave >> 1, wn = wave & 1;
-    const int HoWo = p.rr;                                    // contributing pixels per image
-    const int n_first = (int)(kbeg / HoWo);
-    const __amdgpu_buffer_rsrc_t rsA = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<float *>(p.DY + (REGION ? (long)n_first * p.Ho * p.Wo : kbeg) * p.dy_pitch), 0, (int)X3_OOB, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsB = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<float *>(p.X + (long)n_first * p.H * p.W * p.x_pitch), 0, (int)X3_OOB, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsA = wgrad_dy_rsrc<REGION>(p, it), rsB = wgrad_x_rsrc(p, it);
+    const long kbeg = it.kbeg;
+    const int HoWo = p.rr, n_first = it.n_first;
 
     // loader roles: thread t serves ONE pixel (t >> 4) of the K-step in both operands -- channel quads (t & 15) + 16 j of dy
     // (j < NAP) and of x (j < NBP): one pixel walk and one bounds test per K-step (the kernel used to spend as many VALU
@@ -1836,15 +1797,16 @@ __global__ void __launch_bounds__(256, MR == 2 ? 2 : 1) igemm_wgrad_h2t_kernel(W
     int tdy[NBP], tdx[NBP], cb[NBP];
 #pragma unroll
     for (int j = 0; j < NBP; ++j) {
-        const int jc = j0 + (ONETAP ? 0 : 64 * j);
-        const int rs = jc / p.Cin;
-        const int r = rs / p.S;
-        tdy[j] = r * p.dil - p.pad;
-        tdx[j] = (rs - r * p.S) * p.dil - p.pad;
-        cb[j] = j0 + 64 * j - rs * p.Cin;                     // first channel of the group inside its tap
+        const WgradCol c = wgrad_col<ONETAP>(p, j0, j0 + 64 * j);
+        tdy[j] = c.r * p.dil - p.pad;
+        tdx[j] = c.s * p.dil - p.pad;
+        cb[j] = c.ch;                                         // first channel of the group inside its tap
     }
     // pixel walk: the position of the thread's pixel of the current K-step, advanced by BK per step (Wo >= BK: at most one
-    // row wrap).  Narrow images and regions take the division path.
+    // row wrap).  Narrow images and regions take the division path, from the pixel's index in every step.  The kernel keeps its
+    // own three integers instead of wgrad_cols.h's WgradWalk: on the walker, the instances with both K-loops took 10 more VGPRs
+    // (128 x 128: 160 -> 170, 3 -> 2 waves per SIMD) and the 128 x 256 ones 12 -> 104 bytes of scratch per lane beside their
+    // 128 accumulator registers (profiles/wgrad_refactor_resources.txt).
     int pn, py, px_;
     {
         const long m = kbeg + pb0;
@@ -1879,7 +1841,7 @@ __global__ void __launch_bounds__(256, MR == 2 ? 2 : 1) igemm_wgrad_h2t_kernel(W
         const int dyoff = (REGION ? ((n * p.Ho + y) * p.Wo + x) * p.dy_pitch : mk * p.dy_pitch) + cha;
 #pragma unroll
         for (int j = 0; j < NAP; ++j) {
-            const unsigned bo = x3_oob_unless((unsigned)(dyoff + 64 * j) * 4u, inb & (int)(cha + 64 * j < p.Cout));
+            const unsigned bo = oob_unless((unsigned)(dyoff + 64 * j) * 4u, inb & (int)(cha + 64 * j < p.Cout));
             ra[j] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsA, (int)bo, 0, 0));
         }
         const int ys = y * p.stride, xs = x * p.stride;
@@ -1889,7 +1851,7 @@ __global__ void __launch_bounds__(256, MR == 2 ? 2 : 1) igemm_wgrad_h2t_kernel(W
             const int xoff = ((n * p.H + sy) * p.W + sx) * p.x_pitch + cb[0] + 4 * q0;
 #pragma unroll
             for (int j = 0; j < NBP; ++j) {
-                const unsigned bo = x3_oob_unless((unsigned)(xoff + 64 * j) * 4u, v & (int)(j0 + 64 * j + 4 * q0 < Ktot));
+                const unsigned bo = oob_unless((unsigned)(xoff + 64 * j) * 4u, v & (int)(j0 + 64 * j + 4 * q0 < p.Ktot));
                 rb[j] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsB, (int)bo, 0, 0));
             }
         } else {
@@ -1897,8 +1859,8 @@ __global__ void __launch_bounds__(256, MR == 2 ? 2 : 1) igemm_wgrad_h2t_kernel(W
             for (int j = 0; j < NBP; ++j) {
                 const int sy = ys + tdy[j], sx = xs + tdx[j];
                 const int v = inb & (int)((unsigned)sy < (unsigned)p.H) & (int)((unsigned)sx < (unsigned)p.W) &
-                              (int)(j0 + 64 * j + 4 * q0 < Ktot);
-                const unsigned bo = x3_oob_unless((unsigned)(((n * p.H + sy) * p.W + sx) * p.x_pitch + cb[j] + 4 * q0) * 4u, v);
+                              (int)(j0 + 64 * j + 4 * q0 < p.Ktot);
+                const unsigned bo = oob_unless((unsigned)(((n * p.H + sy) * p.W + sx) * p.x_pitch + cb[j] + 4 * q0) * 4u, v);
                 rb[j] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsB, (int)bo, 0, 0));
             }
         }
@@ -1935,19 +1897,10 @@ __global__ void __launch_bounds__(256, MR == 2 ? 2 : 1) igemm_wgrad_h2t_kernel(W
     };
 
     f32x16 acc[MR][NR];
-#pragma unroll
-    for (int mr = 0; mr < MR; ++mr)
-#pragma unroll
-        for (int nr = 0; nr < NR; ++nr)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) acc[mr][nr][e] = 0.f;
+    wgrad_clear(acc);
 
     const int arow0 = wm * 32 * MR, brow0 = wn * 32 * NR;
-    // fragment addressing: 16-lane group gi = lane >> 4 serves rows 16 (gi & 1) .. +15 of a 32-row tile and the k half
-    // gi >> 1; inside the group lane q points at pixel row 8 (gi >> 1) + q / 4 (+ 4 for the second read), channels 4 (q % 4)
-    const int gi = lane >> 4, q16 = lane & 15;
-    const int fa = (8 * (gi >> 1) + (q16 >> 2)) * PIA + (arow0 + 16 * (gi & 1) + 4 * (q16 & 3)) * 2;
-    const int fb = (8 * (gi >> 1) + (q16 >> 2)) * PIB + (brow0 + 16 * (gi & 1) + 4 * (q16 & 3)) * 2;
+    const int fa = wgrad_frag_padded(lane, arow0, PIA), fb = wgrad_frag_padded(lane, brow0, PIB);
     auto mma = [&](int buf) {
         const char *As = smem + buf * STAGE, *Bs = As + 2 * PLA;
         f16x8 a[MR][2], b[NR][2];
@@ -2008,39 +1961,8 @@ __global__ void __launch_bounds__(256, MR == 2 ? 2 : 1) igemm_wgrad_h2t_kernel(W
     if (incr) k_loop(std::true_type{});
     else k_loop(std::false_type{});
 
-    float *out = p.OUT + (long)split * p.split_stride;
-    const float inv_a = pow2f(-ka), inv_b = pow2f(-kb);
-    const int l31 = lane & 31, kh = lane >> 5;
-    if (i0 + BM <= p.Cout && j0 + BN <= Ktot && !(p.beta && gridDim.z == 1)) {
-        // the tile lies inside the weight tensor and is a split-K partial (or overwrites): scale and store, nothing to test
-        // (the general loop below is ~2 300 instructions in ~250 basic blocks; a workgroup's K-loop is ~10 000)
-#pragma unroll
-        for (int mr = 0; mr < MR; ++mr)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) {
-                float *drow = out + (long)(i0 + arow0 + mr * 32 + 4 * kh + (e & 3) + 8 * (e >> 2)) * Ktot + j0 + brow0 + l31;
-#pragma unroll
-                for (int nr = 0; nr < NR; ++nr) drow[nr * 32] = (acc[mr][nr][e] * inv_a) * inv_b;
-            }
-        return;
-    }
-#pragma unroll
-    for (int mr = 0; mr < MR; ++mr) {
-        const int rbase = i0 + arow0 + mr * 32 + 4 * kh;
-#pragma unroll
-        for (int e = 0; e < 16; ++e) {
-            const int co = rbase + (e & 3) + 8 * (e >> 2);
-            if (co >= p.Cout) continue;
-            float *drow = out + (long)co * Ktot + j0 + brow0 + l31;
-#pragma unroll
-            for (int nr = 0; nr < NR; ++nr) {
-                if (j0 + brow0 + nr * 32 + l31 >= Ktot) continue;
-                float v = (acc[mr][nr][e] * inv_a) * inv_b;
-                if (p.beta && gridDim.z == 1) v += drow[nr * 32];
-                drow[nr * 32] = v;
-            }
-        }
-    }
+    wgrad_store_tile<MR, NR, true>(acc, p.OUT + (long)it.split * p.split_stride, i0, j0, arow0, brow0, p.Cout, p.Ktot,
+                                   p.beta && gridDim.z == 1, pow2f(-ka), pow2f(-kb));
 }
 
 #include "igemm_h2dw.inc"

@@ -110,9 +110,9 @@ __global__ void __launch_bounds__(256, 2) conv_h2d_kernel(IgemmParams p) {
             __builtin_amdgcn_raw_ptr_buffer_load_lds(rsB, (__attribute__((address_space(3))) void *)(st + bdst[i]), 16,
                                                      (int)(bbase[i] + (unsigned)kt * kstride), 0, 0, 0);
         __builtin_amdgcn_raw_ptr_buffer_load_lds(rsA, (__attribute__((address_space(3))) void *)(st + wave * 1024), 16,
-                                                 (int)x3_oob_unless(b0, v), 0, 0, 0);
+                                                 (int)oob_unless(b0, v), 0, 0, 0);
         __builtin_amdgcn_raw_ptr_buffer_load_lds(rsA, (__attribute__((address_space(3))) void *)(st + PA + wave * 1024), 16,
-                                                 (int)x3_oob_unless(b0 + (unsigned)plane_b, v), 0, 0, 0);
+                                                 (int)oob_unless(b0 + (unsigned)plane_b, v), 0, 0, 0);
     };
 
     f32x16 acc[MR][NR];

@@ -2,19 +2,20 @@
 // RCF_CONV_X_PLANES + RCF_CONV_DY_PLANES: x from bn_apply, dy from bn_bwd_apply) and delivered global -> LDS by DMA: the kernel
 // that splits nothing.  igemm_wgrad_h2t_kernel spends 4.2 VALU instructions per MFMA on loading, splitting and storing both of
 // its operands (it is the step's largest family and power-limited: DESIGN.md); here a K-step's VALU work is one pixel walk and
-// the address arithmetic of GA + GB DMA pieces per thread.  Included by igemm_conv.hip (WgradParams, lds_tr16).
+// the address arithmetic of GA + GB DMA pieces per thread.  Included by igemm_conv.hip; built on wgrad_cols.h.
 //
 // dw[co][rs][c] = sum_m dy[m][co] * x[src(m, rs)][c]: rows i = co (128), cols j = (rs, c) (64 NR), K = pixels, 16 per step.
 // LDS image per stage, operand and plane: [64-channel group][16 pixels][128 B]; a wave DMA instruction (1 KB, lane-linear) is
 // 8 pixel rows of one group of one plane, so wave w serves pixel half w & 1 of plane w >> 1 in ALL of its pieces: one pixel
 // walk and one bounds test per thread and K-step.  The 16-byte chunks of pixel row r are XOR-swizzled by ((r >> 1) & 1) << 2
-// (source address and fragment address alike, as in wgrad_bf16_dma_kernel): the 4 rows x 4 chunks a 32-lane half reads through
-// ds_read_b64_tr_b16 cover all 16 chunk positions of the 256-byte bank space.  Three stages (24 KB each at NR = 4: two
-// workgroups per CU), one barrier per K-step, the pieces of step t + 2 issued among the MFMAs of step t.
+// (source address and fragment address alike: wgrad_cols.h wgrad_frag_swizzled, as in wgrad_bf16_dma_kernel).  Three stages
+// (24 KB each at NR = 4: two workgroups per CU), one barrier per K-step, the pieces of step t + 2 issued among the MFMAs of
+// step t (wgrad_cols.h wgrad_dma_kloop).
 // Same three partial products per (pixel, co, c) as igemm_wgrad_h2t_kernel, summed over the same pixel chunks in the same order.
+
 // one K-step: fragments of both planes through the transposing reads, three partial products.  `S` is __restrict__ on purpose:
 // inlined, the reads carry no-alias scopes against the kernel's LDS-DMA writes (see wgrad_tr_step in igemm_bf16.hip).
-template <int MR, int NR, int GA, int GB, int GSZ>
+template <int MR, int NR, int GA, int GB, int GSZ, int PLA>
 __device__ __forceinline__ void wgrad_h2d_step(const char *__restrict__ S, const int (&fa)[MR], const int (&fb)[NR],
                                                f32x16 (&acc)[MR][NR]) {
     f16x8 a[MR][2], b[NR][2];
@@ -30,8 +31,8 @@ __device__ __forceinline__ void wgrad_h2d_step(const char *__restrict__ S, const
     for (int nr = 0; nr < NR; ++nr)
 #pragma unroll
         for (int pl = 0; pl < 2; ++pl) {
-            const u32x2 lo = lds_tr16(S + pl * GB * GSZ + fb[nr]);
-            const u32x2 hi = lds_tr16(S + pl * GB * GSZ + fb[nr] + 4 * 128);
+            const u32x2 lo = lds_tr16(S + PLA + pl * GB * GSZ + fb[nr]);
+            const u32x2 hi = lds_tr16(S + PLA + pl * GB * GSZ + fb[nr] + 4 * 128);
             b[nr][pl] = __builtin_bit_cast(f16x8, u32x4{lo[0], lo[1], hi[0], hi[1]});
         }
     constexpr int HA[3] = {1, 0, 0}, HB[3] = {0, 1, 0};
@@ -44,213 +45,17 @@ __device__ __forceinline__ void wgrad_h2d_step(const char *__restrict__ S, const
                 acc[mr][nr] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[mr][HA[t]], b[nr][HB[t]], acc[mr][nr], 0, 0, 0);
 }
 
+struct WgradOpH2 {
+    typedef float T;                                           // a pixel is 4 * pitch bytes ([h: C fp16 | m: C fp16]), like the fp32 tensor it replaces
+    static constexpr int BK = 16, PLANES = 2, PASSES = 3;
+    static constexpr bool SCALED = true;
+    template <int MR, int NR, int PLA>
+    static __device__ __forceinline__ void mma(const char *S, const int (&fa)[MR], const int (&fb)[NR], f32x16 (&acc)[MR][NR]) {
+        wgrad_h2d_step<MR, NR, PLA / (2 * BK * 128), NR, BK * 128, PLA>(S, fa, fb, acc);
+    }
+};
 template <int NR, bool REGION, bool ONETAP>
 __global__ void __launch_bounds__(256, 2) igemm_wgrad_h2d_kernel(WgradParams p) {
-    constexpr int MR = 2, BM = 64 * MR, BN = 64 * NR, BKP = 16;
-    constexpr int GA = BM / 64, GB = BN / 64;                  // channel groups per plane
-    constexpr int GSZ = BKP * 128;                             // one group of one plane: 16 pixels x 128 B
-    constexpr int PLA = 2 * GA * GSZ, PLB = 2 * GB * GSZ, STAGE = PLA + PLB;
-    constexpr int NLD = GA + GB;
-    __shared__ __attribute__((aligned(16))) char smem[3 * STAGE];
-
-    int tile, split;
-    rcf_wgrad_item(p.xcd_map, tile, split);
-    int tile_i, tile_j;
-    rcf_wgrad_tile_ij(tile, p.itiles, p.jtiles, p.cblocks, tile_i, tile_j);
-    const int i0 = tile_i * BM, j0 = tile_j * BN;
-    const int Ktot = p.R * p.S * p.Cin;
-    const long kbeg = (long)split * p.chunk;
-    const long kend = min(p.M, kbeg + p.chunk);
-    const int klen = (int)(kend - kbeg);
-
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wm = wave >> 1, wn = wave & 1;
-    const int HoWo = p.rr;
-    const int n_first = (int)(kbeg / HoWo);
-    // descriptors over the planes: a pixel is 4 * pitch bytes ([h: C fp16 | m: C fp16]), like the fp32 tensor it replaces
-    const __amdgpu_buffer_rsrc_t rsA = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<float *>(p.DY + (REGION ? (long)n_first * p.Ho * p.Wo : kbeg) * p.dy_pitch), 0, (int)X3_OOB, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsB = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<float *>(p.X + (long)n_first * p.H * p.W * p.x_pitch), 0, (int)X3_OOB, 0x00020000);
-
-    // this thread's pixel row of the K-step, its plane, and its chunk position inside a 128-byte group row
-    const int plane = wave >> 1;
-    const int prow = 8 * (wave & 1) + (lane >> 3), qpos = lane & 7;
-    const int qsrc = qpos ^ (((prow >> 1) & 1) << 2);          // source chunk of that position
-    const int pla_b = plane * 2 * p.dy_pitch, plb_b = plane * 2 * p.x_pitch;     // byte offset of the plane inside a pixel
-    int pn, py, px, ppix;                                      // the pixel walk (image index relative to n_first)
-    {
-        const long m = kbeg + prow;
-        pn = (int)(m / HoWo);
-        ppix = (int)(m - (long)pn * HoWo);
-        if (REGION) region_yx(ppix, p.ry0, p.rx0, p.rh, p.rw, p.rband, py, px);
-        else { py = ppix / p.Wo; px = ppix - py * p.Wo; }
-        pn -= n_first;
-    }
-    const bool incr = !REGION && p.Wo >= BKP;
-    int cha[GA], chb[GB], tr[GB], ts[GB];
-    bool acta[GA], actb[GB];
-#pragma unroll
-    for (int g = 0; g < GA; ++g) {
-        cha[g] = i0 + 64 * g + 8 * qsrc;
-        acta[g] = cha[g] < p.Cout;
-    }
-#pragma unroll
-    for (int g = 0; g < GB; ++g) {
-        const int jc = j0 + 64 * g + 8 * qsrc;                 // GEMM column = (tap, channel)
-        const int rs = (ONETAP ? j0 : jc) / p.Cin;
-        chb[g] = jc - rs * p.Cin;
-        tr[g] = rs / p.S;
-        ts[g] = rs - tr[g] * p.S;
-        actb[g] = jc < Ktot;
-    }
-    auto loads = [&](int kt, int stage) {
-        char *As = smem + stage * STAGE + plane * GA * GSZ + (wave & 1) * 1024;
-        char *Bs = smem + stage * STAGE + PLA + plane * GB * GSZ + (wave & 1) * 1024;
-        const int mk = kt * BKP + prow;
-        const bool inb = mk < klen;
-        const int dyoff = REGION ? ((pn * p.Ho + py) * p.Wo + px) * p.dy_pitch : mk * p.dy_pitch;
-#pragma unroll
-        for (int g = 0; g < GA; ++g) {
-            const unsigned bo = x3_oob_unless((unsigned)dyoff * 4u + (unsigned)(pla_b + cha[g] * 2), (int)inb & (int)acta[g]);
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsA, (__attribute__((address_space(3))) void *)(As + g * GSZ), 16, (int)bo, 0, 0, 0);
-        }
-        if constexpr (ONETAP) {
-            const int sy = py * p.stride - p.pad + tr[0] * p.dil, sx = px * p.stride - p.pad + ts[0] * p.dil;
-            const int v = (int)inb & (int)((unsigned)sy < (unsigned)p.H) & (int)((unsigned)sx < (unsigned)p.W);
-            const int xoff = ((pn * p.H + sy) * p.W + sx) * p.x_pitch;
-#pragma unroll
-            for (int g = 0; g < GB; ++g) {
-                const unsigned bo = x3_oob_unless((unsigned)xoff * 4u + (unsigned)(plb_b + chb[g] * 2), (int)v & (int)actb[g]);
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(rsB, (__attribute__((address_space(3))) void *)(Bs + g * GSZ), 16, (int)bo, 0, 0, 0);
-            }
-        } else {
-#pragma unroll
-            for (int g = 0; g < GB; ++g) {
-                const int sy = py * p.stride - p.pad + tr[g] * p.dil, sx = px * p.stride - p.pad + ts[g] * p.dil;
-                const int v = (int)inb & (int)actb[g] & (int)((unsigned)sy < (unsigned)p.H) & (int)((unsigned)sx < (unsigned)p.W);
-                const unsigned bo = x3_oob_unless((unsigned)(((pn * p.H + sy) * p.W + sx) * p.x_pitch) * 4u + (unsigned)(plb_b + chb[g] * 2), v);
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(rsB, (__attribute__((address_space(3))) void *)(Bs + g * GSZ), 16, (int)bo, 0, 0, 0);
-            }
-        }
-    };
-    auto advance_rows = [&]() {                  // Wo >= 16: at most one row wrap per K-step (no branches)
-        px += BKP;
-        const bool wx = px >= p.Wo;
-        px -= wx ? p.Wo : 0;
-        py += wx ? 1 : 0;
-        const bool wy = py == p.Ho;
-        py = wy ? 0 : py;
-        pn += wy ? 1 : 0;
-    };
-    auto issue = [&](int kt, int stage) {
-        loads(kt, stage);
-        if (incr) {
-            advance_rows();
-        } else {
-            ppix += BKP;
-            while (ppix >= HoWo) { ppix -= HoWo; ++pn; }
-            if (REGION) region_yx(ppix, p.ry0, p.rx0, p.rh, p.rw, p.rband, py, px);
-            else { py = ppix / p.Wo; px = ppix - py * p.Wo; }
-        }
-    };
-
-    f32x16 acc[MR][NR];
-#pragma unroll
-    for (int mr = 0; mr < MR; ++mr)
-#pragma unroll
-        for (int nr = 0; nr < NR; ++nr)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) acc[mr][nr][e] = 0.f;
-
-    const int arow0 = wm * 32 * MR, brow0 = wn * 32 * NR;
-    // fragment addressing: 16-lane group gi serves tile rows (channels) 16 (gi & 1) .. +15 and the k half gi >> 1; lane q of the
-    // group points at pixel row 8 (gi >> 1) + q / 4 (+ 4 for the second read), channels 4 (q % 4) .. + 3 of its 16
-    const int gi = lane >> 4, q16 = lane & 15;
-    const int fprow = 8 * (gi >> 1) + (q16 >> 2);
-    const int swz = ((fprow >> 1) & 1) << 2;                   // (+ 4 leaves bit 1 of the pixel row alone)
-    const int cin = 16 * (gi & 1) + 4 * (q16 & 3);             // channel inside a 32-channel tile
-    const int wi = (cin & 7) * 2;
-    int fa[MR], fb[NR];
-#pragma unroll
-    for (int mr = 0; mr < MR; ++mr) {
-        const int c = arow0 + mr * 32 + cin;
-        fa[mr] = (c >> 6) * GSZ + fprow * 128 + ((((c >> 3) & 7) ^ swz) << 4) + wi;
-    }
-#pragma unroll
-    for (int nr = 0; nr < NR; ++nr) {
-        const int c = brow0 + nr * 32 + cin;
-        fb[nr] = PLA + (c >> 6) * GSZ + fprow * 128 + ((((c >> 3) & 7) ^ swz) << 4) + wi;
-    }
-    auto mma = [&](const char *S) { wgrad_h2d_step<MR, NR, GA, GB, GSZ>(S, fa, fb, acc); };
-
-    const int KT = (klen + BKP - 1) / BKP;
-    issue(0, 0);
-    if (KT > 1) issue(1, 1);
-    if (KT > 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NLD) : "memory");
-    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    int st = 0, kt = 0;
-    if (incr) {
-        // steady state as ONE basic block: fragment reads, then one LDS-DMA piece behind each of the first MFMAs
-        for (; kt + 2 < KT; ++kt) {
-            const int st2 = st >= 1 ? st - 1 : 2;         // (st + 2) % 3
-            mma(smem + st * STAGE);
-            loads(kt + 2, st2);
-            advance_rows();
-            __builtin_amdgcn_sched_group_barrier(0x100, 4 * (MR + NR), 0);
-#pragma unroll
-            for (int i = 0; i < NLD; ++i) {
-                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                __builtin_amdgcn_sched_group_barrier(0x010, 1, 0);
-            }
-            __builtin_amdgcn_sched_group_barrier(0x008, 3 * MR * NR - NLD, 0);
-            asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(NLD) : "memory");
-            __builtin_amdgcn_s_barrier();
-            st = st == 2 ? 0 : st + 1;
-        }
-    }
-    for (; kt < KT; ++kt) {
-        const int st2 = st >= 1 ? st - 1 : 2;
-        if (kt + 2 < KT) issue(kt + 2, st2);
-        mma(smem + st * STAGE);
-        if (kt + 2 < KT) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NLD) : "memory");
-        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        st = st == 2 ? 0 : st + 1;
-    }
-
-    float *out = p.OUT + (long)split * p.split_stride;
-    const float inv_a = pow2f(-h2_exponent(*p.amax_a)), inv_b = pow2f(-h2_exponent(*p.amax_b));
-    const int l31 = lane & 31, kh = lane >> 5;
-    if (i0 + BM <= p.Cout && j0 + BN <= Ktot && !(p.beta && gridDim.z == 1)) {
-        // the tile lies inside the weight tensor and is a split-K partial (or overwrites): scale and store, nothing to test
-#pragma unroll
-        for (int mr = 0; mr < MR; ++mr)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) {
-                float *drow = out + (long)(i0 + arow0 + mr * 32 + 4 * kh + (e & 3) + 8 * (e >> 2)) * Ktot + j0 + brow0 + l31;
-#pragma unroll
-                for (int nr = 0; nr < NR; ++nr) drow[nr * 32] = (acc[mr][nr][e] * inv_a) * inv_b;
-            }
-        return;
-    }
-#pragma unroll
-    for (int mr = 0; mr < MR; ++mr) {
-        const int rbase = i0 + arow0 + mr * 32 + 4 * kh;
-#pragma unroll
-        for (int e = 0; e < 16; ++e) {
-            const int co = rbase + (e & 3) + 8 * (e >> 2);
-            if (co >= p.Cout) continue;
-            float *drow = out + (long)co * Ktot + j0 + brow0 + l31;
-#pragma unroll
-            for (int nr = 0; nr < NR; ++nr) {
-                if (j0 + brow0 + nr * 32 + l31 >= Ktot) continue;
-                float v = (acc[mr][nr][e] * inv_a) * inv_b;
-                if (p.beta && gridDim.z == 1) v += drow[nr * 32];
-                drow[nr * 32] = v;
-            }
-        }
-    }
+    __shared__ __attribute__((aligned(16))) char smem[3 * (2 + NR) * 2 * WgradOpH2::BK * 128];
+    wgrad_dma_body<WgradOpH2, NR, REGION, ONETAP>(p, smem);
 }

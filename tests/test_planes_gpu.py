@@ -14,22 +14,10 @@ import torch.nn.functional as F
 
 import rcf_amd
 from rcf_amd import ops
+from wgrad_cases import to_planes
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
-
-
-def to_planes(x, bound_bits):
-    """x [N,H,W,C] fp32 on the device -> the fp32-typed pair-plane buffer the kernels read, scaled like they scale: 2^k with
-    k = 14 - floor(log2(bound))"""
-    b = float(bound_bits.view(torch.float32))
-    k = 14 - int(np.floor(np.log2(b)))
-    t = x.double() * 2.0 ** k
-    h = t.to(torch.float16)
-    m = (t - h.double()).to(torch.float16)
-    N, H, W, C = x.shape
-    pl = torch.stack([h, m], dim=3).contiguous()                    # [N,H,W,2,C] fp16 = [pixel][h | m]
-    return pl.view(torch.float32).reshape(N, H, W, C), k
 
 
 def from_planes(buf, k):
