@@ -926,6 +926,49 @@ int rcf_ncut_refine_packed_f32(const uint32_t *bits, const int32_t *deg, int n, 
 int rcf_mask_merge_u8(const float *a, const float *b, int frames, long npix, long long umi_th, uint8_t *out, long long *counts,
                       void *stream);
 
+/* ---- PWC-Lite (models/amd/pwc_lite.py; csrc/pwc.hip, the resize adjoint in csrc/spatial.hip) -----------------------------------
+ * The pieces between the native convs, rcf_correlation_* and rcf_flow_warp_*.  fp32, no atomics, every sum in a fixed order: the
+ * same bits on every call.  Every entry point returns RCF_EINVAL before any launch -- sizes and ranges first, then pointers.
+ * hw: pixels of one image (0 < hw < 2^30); 1 <= M <= rcf_pwc_geometry(1) masks; 0 < B <= 65535.
+ * rcf_pwc_geometry(which): 0 pixels per workgroup of the pooled sums, 1 the largest M, 2 the largest C of a pooled slice, 3 pixels
+ * per workgroup of pack / unpack, 4 the most channels one pack writes; 0 for any other `which`.
+ *
+ * Segment pooling (get_averge_feat, pwc_lite.py:85-96, all masks at once): feat an NHWC channel slice [B][hw][C] at pixel pitch
+ * feat_pitch (C % 4 == 0, 4 <= C <= geometry(2), pitch % 4 == 0, 16-byte aligned), mask planar [B][M][hw]:
+ *   pooled[b][m][c] = sum_p feat mask / sum_p mask,  msum[b][m] = sum_p mask      (fp64 sums; a zero sum divides by zero, no guard)
+ * partials: rcf_pwc_pool_partials(B, M, C, hw) doubles (RCF_EWORKSPACE when partials_len is less; 0 for a refused shape).
+ * Backward, from the forward's pooled and msum:
+ *   dfeat[b][p][c] (beta ? += : =) sum_m mask dpooled / msum           (an NHWC slice at dfeat_pitch)
+ *   dmask[b][m][p] = (sum_c feat dpooled - sum_c pooled dpooled) / msum */
+int rcf_pwc_geometry(int which);
+long rcf_pwc_pool_partials(int B, int M, int C, int hw);
+int rcf_pwc_segment_pool_fwd_f32(const float *feat, int feat_pitch, const float *mask, float *pooled, float *msum, double *partials,
+                                 long partials_len, int B, int M, int C, int hw, void *stream);
+int rcf_pwc_segment_pool_bwd_f32(const float *feat, int feat_pitch, const float *mask, const float *pooled, const float *msum,
+                                 const float *dpooled, float *dfeat, int dfeat_pitch, int beta, float *dmask, int B, int M, int C, int hw,
+                                 void *stream);
+/* Segment flow composition: flow[b][c][p] = sum_m mask[b][m][p] group[b][m][c] with group [B][M][2], flow planar [B][2][hw].
+ * Backward: dmask[b][m][p] (beta ? += : =) sum_c dflow group (dmask may be NULL: a constant mask), dgroup[b][m][c] = sum_p mask dflow
+ * through rcf_pwc_flow_partials(B, M, hw) doubles of partials. */
+long rcf_pwc_flow_partials(int B, int M, int hw);
+int rcf_pwc_segment_flow_fwd_f32(const float *mask, const float *group, float *flow, int B, int M, int hw, void *stream);
+int rcf_pwc_segment_flow_bwd_f32(const float *mask, const float *group, const float *dflow, float *dmask, int beta, float *dgroup,
+                                 double *partials, long partials_len, int B, int M, int hw, void *stream);
+/* g = dy (y > 0 ? 1 : slope) on `rows` rows of C channels (C % 4 == 0), every tensor at its own pitch (% 4 == 0, >= C), 16-byte
+ * aligned; y is the LeakyReLU's OUTPUT (a positive slope keeps the sign), y = +-0 takes the slope. */
+int rcf_pwc_leaky_bwd_f32(const float *dy, long dy_pitch, const float *y, long y_pitch, float *g, long g_pitch, long rows, int C,
+                          float slope, void *stream);
+/* The estimator's input pack: planar corr [B][D][hw] and flow [B][2][hw] -> channels c0 .. c0 + D + 1 of the NHWC buffer
+ * buf[B][hw][buf_pitch], then zeros up to the next multiple of 4 (the guard channels of a conv whose Cin % 4 == 0); channels outside
+ * that range are left alone.  c0 % 4 == 0, buf_pitch % 4 == 0, at most geometry(4) channels.  rcf_pwc_unpack_f32 is the adjoint:
+ * dcorr[b][k][p] = dbuf[b][p][c0 + k], dflow[b][c][p] = dbuf[b][p][c0 + D + c]. */
+int rcf_pwc_pack_f32(const float *corr, const float *flow, float *buf, int buf_pitch, int c0, int D, int B, int hw, void *stream);
+int rcf_pwc_unpack_f32(const float *dbuf, int buf_pitch, int c0, float *dcorr, float *dflow, int D, int B, int hw, void *stream);
+/* The adjoint of rcf_resize_bilinear_nchw_f32 in gather form: dx [planes][Hi][Wi] = R^T dy [planes][Ho][Wo]; either align_corners
+ * setting, any size ratio; an input pixel that no output tap names is written as 0. */
+int rcf_resize_bilinear_nchw_bwd_f32(const float *dy, float *dx, int planes, int Hi, int Wi, int Ho, int Wo, int align_corners,
+                                     void *stream);
+
 #ifdef __cplusplus
 }
 #endif

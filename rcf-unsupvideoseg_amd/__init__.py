@@ -15,5 +15,6 @@ from .flow_head import CompactnessHead, FlowAggregationHeadWithResidual  # noqa:
 from .model import RCFModel  # noqa: F401
 from .ops import flow_warp, occu_mask_backward as get_occu_mask_backward  # noqa: F401
 from .ops import occu_mask_bidirection as get_occu_mask_bidirection  # noqa: F401
+from .pwc_lite import PWCLite  # noqa: F401
 from .trainer import Trainer, poly_lr_factor  # noqa: F401
 from .unflow_loss import unFlowLoss  # noqa: F401

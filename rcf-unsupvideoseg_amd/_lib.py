@@ -202,6 +202,17 @@ PROTOS = {
     "rcf_unflow_smooth_fwd_f32": (c_int, [P, c_long, P, c_float, c_float, c_int, P, P, c_int, c_int, c_int, P]),
     "rcf_unflow_smooth_bwd_f32": (c_int, [P, c_long, P, c_float, c_float, c_int, P, P, c_int, c_int, c_int, P]),
     "rcf_unflow_area_f32": (c_int, [P, c_long, P, c_int, c_int, c_int, c_int, c_int, P]),
+    "rcf_pwc_geometry": (c_int, [c_int]),
+    "rcf_pwc_pool_partials": (c_long, [c_int, c_int, c_int, c_int]),
+    "rcf_pwc_flow_partials": (c_long, [c_int, c_int, c_int]),
+    "rcf_pwc_segment_pool_fwd_f32": (c_int, [P, c_int, P, P, P, P, c_long, c_int, c_int, c_int, c_int, P]),
+    "rcf_pwc_segment_pool_bwd_f32": (c_int, [P, c_int, P, P, P, P, P, c_int, c_int, P, c_int, c_int, c_int, c_int, P]),
+    "rcf_pwc_segment_flow_fwd_f32": (c_int, [P, P, P, c_int, c_int, c_int, P]),
+    "rcf_pwc_segment_flow_bwd_f32": (c_int, [P, P, P, P, c_int, P, P, c_long, c_int, c_int, c_int, P]),
+    "rcf_pwc_leaky_bwd_f32": (c_int, [P, c_long, P, c_long, P, c_long, c_long, c_int, c_float, P]),
+    "rcf_pwc_pack_f32": (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_int, P]),
+    "rcf_pwc_unpack_f32": (c_int, [P, c_int, c_int, P, P, c_int, c_int, c_int, P]),
+    "rcf_resize_bilinear_nchw_bwd_f32": (c_int, [P, P, c_int, c_int, c_int, c_int, c_int, c_int, P]),
     "rcf_crf_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "rcf_crf_soft": (c_int, [P, P, c_int, c_int, c_int, c_float, c_float, c_float, c_float, c_float, c_int, P, P, P,
                              P, c_size_t, P]),

@@ -501,6 +501,37 @@ __global__ void __launch_bounds__(256) resize_nchw_kernel(const float *__restric
     }
 }
 
+// The adjoint of resize_nchw_kernel in gather form: input pixel (pl, yi, xi) sums dy over the output pixels whose taps name it, rows
+// upwards, columns upwards, zero weights skipped -- the walk of resize_bwd_pixel on planes.  A pixel that no tap names (most of
+// them when the resize shrinks the image) is written as 0.  Per element the error is (terms + 7) 2^-24 mass: 1 - lambda and the
+// sum of two clamped taps on either axis, wy wx, times dy, terms - 1 additions, plus 2.
+__global__ void __launch_bounds__(256) resize_nchw_bwd_kernel(const float *__restrict__ dy, float *__restrict__ dx, int planes, int Hi,
+                                                              int Wi, int Ho, int Wo, int align, float sh, float sw) {
+    const long total = (long)planes * Hi * Wi;
+    const long step = (long)gridDim.x * blockDim.x;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += step) {
+        const int xi = (int)(i % Wi);
+        long t = i / Wi;
+        const int yi = (int)(t % Hi);
+        const long pl = t / Hi;
+        int ylo, yhi, xlo, xhi;
+        cand_range(yi, sh, align, Ho, ylo, yhi);
+        cand_range(xi, sw, align, Wo, xlo, xhi);
+        const float *g = dy + pl * Ho * Wo;
+        float acc = 0.f;
+        for (int yo = ylo; yo <= yhi; ++yo) {
+            const float wy = tap_weight(yo, yi, sh, align, Hi);
+            if (wy == 0.f) continue;
+            for (int xo = xlo; xo <= xhi; ++xo) {
+                const float wx = tap_weight(xo, xi, sw, align, Wi);
+                if (wx == 0.f) continue;
+                acc += g[(long)yo * Wo + xo] * (wy * wx);
+            }
+        }
+        dx[i] = acc;
+    }
+}
+
 // ------------------------------------------------------------------------------------------- layout
 __global__ void __launch_bounds__(256) nchw_to_nhwc_kernel(const float *__restrict__ x, float *__restrict__ y, int N,
                                                            int C, long HW, int Cpad) {
@@ -768,6 +799,16 @@ extern "C" int rcf_resize_bilinear_nchw_f32(const float *x, float *y, int planes
     hipLaunchKernelGGL(resize_nchw_kernel, dim3(ew_blocks((long)planes * Ho * Wo)), dim3(256), 0, rcf_stream(stream), x,
                        y, planes, Hi, Wi, Ho, Wo, align_corners, host_scale(Hi, Ho, align_corners),
                        host_scale(Wi, Wo, align_corners));
+    RCF_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int rcf_resize_bilinear_nchw_bwd_f32(const float *dy, float *dx, int planes, int Hi, int Wi, int Ho, int Wo,
+                                                int align_corners, void *stream) {
+    if (planes <= 0 || Hi <= 0 || Wi <= 0 || Ho <= 0 || Wo <= 0 || (long)Hi * Wi >= (1L << 30) || (long)Ho * Wo >= (1L << 30)) return RCF_EINVAL;
+    if (!dy || !dx) return RCF_EINVAL;
+    hipLaunchKernelGGL(resize_nchw_bwd_kernel, dim3(ew_blocks((long)planes * Hi * Wi)), dim3(256), 0, rcf_stream(stream), dy, dx,
+                       planes, Hi, Wi, Ho, Wo, align_corners, host_scale(Hi, Ho, align_corners), host_scale(Wi, Wo, align_corners));
     RCF_LAUNCH_CHECK();
     return 0;
 }

@@ -1165,6 +1165,132 @@ def area_resize(x, size):
     return out
 
 
+# ------------------------------------------------------------------------------- PWC-Lite (csrc/pwc.hip)
+def _pwc_operands(*ts):
+    _need_cuda(*ts)
+    for t in ts:
+        if t is not None and t.dtype != torch.float32:
+            raise _lib.RcfHipError(f"the PWC-Lite ops take float32 tensors, not {t.dtype}")
+
+
+def _pool_operands(feat, mask):
+    _pwc_operands(feat, mask)
+    if feat.dim() != 4 or mask.dim() != 4 or mask.shape[0] != feat.shape[0] or tuple(mask.shape[2:]) != tuple(feat.shape[1:3]):
+        raise _lib.RcfHipError(f"feat must be NHWC [B, h, w, C] and mask [B, M, h, w]: {tuple(feat.shape)}, {tuple(mask.shape)}")
+    return mask.contiguous()
+
+
+def segment_pool(feat, mask):
+    """feat: NHWC [B, h, w, C] (may be a channel slice), mask: [B, M, h, w] -> (pooled [B, M, C] = sum feat mask / sum mask, the mask
+    sums [B, M]); the reference's get_averge_feat for all masks at once"""
+    mask = _pool_operands(feat, mask)
+    B, h, w, C = feat.shape
+    M = mask.shape[1]
+    n = _lib.load().rcf_pwc_pool_partials(B, M, C, h * w)
+    pooled = torch.empty((B, M, C), dtype=torch.float32, device=feat.device)
+    msum = torch.empty((B, M), dtype=torch.float32, device=feat.device)
+    partials = torch.empty(max(n, 1), dtype=torch.float64, device=feat.device)
+    call("rcf_pwc_segment_pool_fwd_f32", _p(feat), pitch_of(feat), _p(mask), _p(pooled), _p(msum), _p(partials), n, B, M, C, h * w, _stream())
+    return pooled, msum
+
+
+def segment_pool_bwd(feat, mask, pooled, msum, dpooled, dfeat=None, beta=0):
+    """-> (dfeat, dmask); dfeat (an NHWC slice the caller owns, or a new dense tensor) is overwritten (beta 0) or added to (beta 1)"""
+    mask = _pool_operands(feat, mask)
+    _pwc_operands(pooled, msum, dpooled, dfeat)
+    B, h, w, C = feat.shape
+    M = mask.shape[1]
+    if dfeat is None:
+        dfeat = torch.empty((B, h, w, C), dtype=torch.float32, device=feat.device)
+    dmask = torch.empty_like(mask)
+    call("rcf_pwc_segment_pool_bwd_f32", _p(feat), pitch_of(feat), _p(mask), _p(pooled.contiguous()), _p(msum.contiguous()),
+         _p(dpooled.contiguous()), _p(dfeat), pitch_of(dfeat), int(beta), _p(dmask), B, M, C, h * w, _stream())
+    return dfeat, dmask
+
+
+def segment_flow(mask, group):
+    """mask [B, M, h, w], group [B, M, 2] -> flow [B, 2, h, w] = sum_m mask_m group_m"""
+    _pwc_operands(mask, group)
+    B, M, h, w = mask.shape
+    if tuple(group.shape) != (B, M, 2):
+        raise _lib.RcfHipError(f"group must be [B, M, 2] for a mask {tuple(mask.shape)}: {tuple(group.shape)}")
+    flow = torch.empty((B, 2, h, w), dtype=torch.float32, device=mask.device)
+    call("rcf_pwc_segment_flow_fwd_f32", _p(mask.contiguous()), _p(group.contiguous()), _p(flow), B, M, h * w, _stream())
+    return flow
+
+
+def segment_flow_bwd(mask, group, dflow, dmask=None, beta=0, need_dmask=True):
+    """-> (dmask or None, dgroup [B, M, 2]); a given dmask (contiguous, the mask's shape) is overwritten or added to (beta)"""
+    _pwc_operands(mask, group, dflow, dmask)
+    B, M, h, w = mask.shape
+    if tuple(group.shape) != (B, M, 2) or tuple(dflow.shape) != (B, 2, h, w):
+        raise _lib.RcfHipError(f"group must be [B, M, 2] and dflow [B, 2, h, w] for a mask {tuple(mask.shape)}")
+    if need_dmask and dmask is None:
+        dmask, beta = torch.empty((B, M, h, w), dtype=torch.float32, device=mask.device), 0
+    if dmask is not None and (not dmask.is_contiguous() or dmask.shape != mask.shape):
+        raise _lib.RcfHipError("dmask must be contiguous and of the mask's shape")
+    n = _lib.load().rcf_pwc_flow_partials(B, M, h * w)
+    dgroup = torch.empty((B, M, 2), dtype=torch.float32, device=mask.device)
+    partials = torch.empty(max(n, 1), dtype=torch.float64, device=mask.device)
+    call("rcf_pwc_segment_flow_bwd_f32", _p(mask.contiguous()), _p(group.contiguous()), _p(dflow.contiguous()), _p(dmask), int(beta),
+         _p(dgroup), _p(partials), n, B, M, h * w, _stream())
+    return dmask, dgroup
+
+
+def resize_nchw_bwd(dy, in_size, align_corners=False, out=None):
+    """the adjoint of resize_nchw: dy [..., Ho, Wo] -> dx [..., Hi, Wi] (every element of a given contiguous `out` is written)"""
+    _pwc_operands(dy, out)
+    dy = dy.contiguous()
+    Ho, Wo = dy.shape[-2:]
+    Hi, Wi = int(in_size[0]), int(in_size[1])
+    dx = torch.empty(tuple(dy.shape[:-2]) + (Hi, Wi), dtype=torch.float32, device=dy.device) if out is None else out
+    if not dx.is_contiguous() or tuple(dx.shape) != tuple(dy.shape[:-2]) + (Hi, Wi):
+        raise _lib.RcfHipError(f"out must be contiguous and of shape {tuple(dy.shape[:-2]) + (Hi, Wi)}")
+    call("rcf_resize_bilinear_nchw_bwd_f32", _p(dy), _p(dx), dy.numel() // (Ho * Wo), Hi, Wi, Ho, Wo, int(align_corners), _stream())
+    return dx
+
+
+def leaky_bwd(dy, y, slope, out=None):
+    """g = dy * (y > 0 ? 1 : slope) with y the LeakyReLU's output; dy, y and out are NHWC tensors or channel slices"""
+    _pwc_operands(dy, y, out)
+    if dy.shape != y.shape:
+        raise _lib.RcfHipError(f"dy and y must share one shape: {tuple(dy.shape)}, {tuple(y.shape)}")
+    if out is None:
+        out = torch.empty(tuple(dy.shape), dtype=torch.float32, device=dy.device)
+    call("rcf_pwc_leaky_bwd_f32", _p(dy), pitch_of(dy), _p(y), pitch_of(y), _p(out), pitch_of(out), _rows(dy), dy.shape[3], float(slope),
+         _stream())
+    return out
+
+
+def _pack_operands(corr, flow, buf, c0):
+    _pwc_operands(corr, flow, buf)
+    B, D, h, w = corr.shape
+    if tuple(flow.shape) != (B, 2, h, w) or buf.dim() != 4 or tuple(buf.shape[:3]) != (B, h, w):
+        raise _lib.RcfHipError(f"corr [B, D, h, w], flow [B, 2, h, w], buf NHWC [B, h, w, C]: {tuple(corr.shape)}, {tuple(flow.shape)}, "
+                               f"{tuple(buf.shape)}")
+    if buf.shape[3] < (c0 + D + 2 + 3) // 4 * 4:
+        raise _lib.RcfHipError(f"buf has {buf.shape[3]} channels: too few for {D} + 2 from channel {c0}")
+
+
+def pwc_pack(corr, flow, buf, c0):
+    """planar corr [B, D, h, w] and flow [B, 2, h, w] -> channels c0 .. c0 + D + 1 of the NHWC buffer, zeros up to the next multiple of 4"""
+    _pack_operands(corr, flow, buf, c0)
+    B, D, h, w = corr.shape
+    call("rcf_pwc_pack_f32", _p(corr.contiguous()), _p(flow.contiguous()), _p(buf), pitch_of(buf), int(c0), D, B, h * w, _stream())
+    return buf
+
+
+def pwc_unpack(dbuf, c0, D):
+    """the adjoint of pwc_pack -> (dcorr [B, D, h, w], dflow [B, 2, h, w])"""
+    _pwc_operands(dbuf)
+    B, h, w, _ = dbuf.shape
+    dcorr = torch.empty((B, D, h, w), dtype=torch.float32, device=dbuf.device)
+    dflow = torch.empty((B, 2, h, w), dtype=torch.float32, device=dbuf.device)
+    _pack_operands(dcorr, dflow, dbuf, c0)
+    call("rcf_pwc_unpack_f32", _p(dbuf), pitch_of(dbuf), int(c0), _p(dcorr), _p(dflow), D, B, h * w, _stream())
+    return dcorr, dflow
+
+
 # ------------------------------------------------------------------------------- optimiser
 def adam_step(param, grad, exp_avg, exp_avg_sq, lr, step, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0,
               grad_scale=1.0):
