@@ -969,6 +969,26 @@ int rcf_pwc_unpack_f32(const float *dbuf, int buf_pitch, int c0, float *dcorr, f
 int rcf_resize_bilinear_nchw_bwd_f32(const float *dy, float *dx, int planes, int Hi, int Wi, int Ho, int Wo, int align_corners,
                                      void *stream);
 
+/* ---- AMDModel's seam between the tape and the flow network (models/amd/amd_model.py:197-206, models/fcn_head.py:160-170;
+ * csrc/amd.hip).  fp32, one pass each, no atomics, no sums across threads: the same bits on every call.  Every entry point returns
+ * RCF_EINVAL before any launch -- sizes and ranges first, then pointers.
+ * rcf_amd_geometry(which): 0 pixels per workgroup of the softmax kernels, 1 the largest M, 2 the largest I; 0 otherwise.
+ * Mask softmax: logits NHWC [B I][hw][pitch] of images n = b I + i (16-byte aligned, pitch % 4 == 0, pitch >= Cp, Cp 4 or 8, the first
+ * M <= Cp channels live) -> masks planar and frame-major [I][B][M][hw], masks[i][b][.][p] = softmax_c logits[b I + i][p][c]; frame i is
+ * a contiguous [B][M][hw] tensor.  0 < I <= geometry(2), 0 < B, I B <= 65535, 1 <= M <= geometry(1), 0 < hw < 2^30.  A NaN or +inf logit
+ * makes the masks of its pixel NaN (torch's softmax).
+ * Backward: dmasks is a HOST array of I device pointers, frame i's gradient [B][M][hw] or NULL for zeros;
+ *   dlogits[n][p][c] = p_c (dp_c - sum_k p_k dp_k) for c < M, 0 for M <= c < Cp; channels from Cp up to the pitch are left alone.
+ * The logits are not read again. */
+int rcf_amd_geometry(int which);
+int rcf_amd_mask_softmax_fwd_f32(const float *logits, int pitch, float *masks, int I, int B, int M, int Cp, int hw, void *stream);
+int rcf_amd_mask_softmax_bwd_f32(const float *masks, const float *const *dmasks, float *dlogits, int pitch, int I, int B, int M, int Cp,
+                                 int hw, void *stream);
+/* The flow network's input: normalised frames [B][2][3][Hi][Wi] -> two_frame [B][6][Ho][Wo], every channel (x std_c + mean_c) / 255
+ * (mean 123.675, 116.28, 103.53; std 58.395, 57.12, 57.375) and THEN bilinear with align_corners = True, on the float32 source
+ * positions of rcf_resize_bilinear_nchw_f32.  Sizes 1 .. 2^14, 0 < B <= 65535. */
+int rcf_amd_frame_pair_f32(const float *frames, float *out, int B, int Hi, int Wi, int Ho, int Wo, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -13,6 +13,7 @@ from .evaluate import Evaluator  # noqa: F401
 from .crf import CRFHead, crf_hard, crf_soft  # noqa: F401
 from .flow_head import CompactnessHead, FlowAggregationHeadWithResidual  # noqa: F401
 from .model import RCFModel  # noqa: F401
+from .amd_model import AMDModel  # noqa: F401
 from .ops import flow_warp, occu_mask_backward as get_occu_mask_backward  # noqa: F401
 from .ops import occu_mask_bidirection as get_occu_mask_bidirection  # noqa: F401
 from .pwc_lite import PWCLite  # noqa: F401

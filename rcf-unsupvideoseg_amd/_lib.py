@@ -213,6 +213,10 @@ PROTOS = {
     "rcf_pwc_pack_f32": (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_int, P]),
     "rcf_pwc_unpack_f32": (c_int, [P, c_int, c_int, P, P, c_int, c_int, c_int, P]),
     "rcf_resize_bilinear_nchw_bwd_f32": (c_int, [P, P, c_int, c_int, c_int, c_int, c_int, c_int, P]),
+    "rcf_amd_geometry": (c_int, [c_int]),
+    "rcf_amd_mask_softmax_fwd_f32": (c_int, [P, c_int, P, c_int, c_int, c_int, c_int, c_int, P]),
+    "rcf_amd_mask_softmax_bwd_f32": (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, P]),
+    "rcf_amd_frame_pair_f32": (c_int, [P, P, c_int, c_int, c_int, c_int, c_int, P]),
     "rcf_crf_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "rcf_crf_soft": (c_int, [P, P, c_int, c_int, c_int, c_float, c_float, c_float, c_float, c_float, c_int, P, P, P,
                              P, c_size_t, P]),

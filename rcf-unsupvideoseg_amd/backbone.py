@@ -3,8 +3,9 @@
 Same constructor keywords and state-dict keys as the reference components they replace:
   ResNet      models/resnet.py:371-466 (ctor), :630-645 (forward), :598-628 (init); stage assembly
               models/res_layer.py:26-94 (contract_dilation :66-70); Bottleneck :95-302
-  FCNHead     models/fcn_head.py:50-140,142-147,211-218 + models/decode_head.py:45-90,141-170
-Only the options the RCF configs use are implemented; anything else raises.
+  FCNHead     models/fcn_head.py:50-140,142-147,211-218 + models/decode_head.py:45-90,141-170; with create_flownet the AMD
+              baseline's flow head (:71-98, flow_forward :149-209): PWCLite and unFlowLoss, no convs
+Only the options the RCF and AMD configs use are implemented; anything else raises.
 """
 import torch
 import torch.nn as nn
@@ -184,6 +185,16 @@ class ConvModule(nn.Module):
                            planes=planes)
 
 
+class _FlowLossCfg:
+    """attribute access and keys(): what unFlowLoss takes (the reference's Objectview, models/fcn_head.py:30-35)"""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+    def keys(self):
+        return self.__dict__.keys()
+
+
 class FCNHead(nn.Module):
     def __init__(self, in_channels, channels, *, num_classes, num_convs=2, kernel_size=3, concat_input=True,
                  dilation=1, input_stride=1, input_dilation=None, dropout_ratio=0.1, norm_cfg=None, in_index=-1,
@@ -191,8 +202,12 @@ class FCNHead(nn.Module):
                  conv_cfg=None, act_cfg=None, loss_decode=None, ignore_index=255, sampler=None, mask_layer=1,
                  ssim_sz=1, load_flownet=False, freeze_flownet=False, flow_model_path=""):
         super().__init__()
+        self.create_flownet = bool(create_flownet)
+        self.align_corners, self.num_classes, self.mask_layer = align_corners, num_classes, mask_layer
         if create_flownet:
-            raise NotImplementedError("FCNHead(create_flownet=True) is the AMD baseline (PWC-Lite), not RCF")
+            # the AMD baseline's flow head (models/fcn_head.py:71-98): a flow network and its loss, no convs and no conv_seg
+            self._init_flownet(mask_layer, ssim_sz, load_flownet, freeze_flownet, flow_model_path)
+            return
         if concat_input or conv_cfg is not None or sampler is not None or num_convs < 1:
             raise NotImplementedError("FCNHead option off the RCF path (concat_input / conv_cfg / sampler)")
         self.input_transform, self.in_index = input_transform, in_index
@@ -215,6 +230,68 @@ class FCNHead(nn.Module):
         self.keep_mask = None           # tests may inject a Dropout2d keep-mask [N, channels]
         self.commute_upsample = True    # layers.commuted_concat_conv when its conditions hold
 
+    # ------------------------------------------------------------------ the AMD baseline's flow head (create_flownet)
+    flow_size = (384, 640)              # the size the flow network and its loss run at (models/fcn_head.py:166-167)
+
+    def _init_flownet(self, mask_layer, ssim_sz, load_flownet, freeze_flownet, flow_model_path):
+        from .pwc_lite import PWCLite
+        from .unflow_loss import unFlowLoss
+        self.flownet = PWCLite(mask_layer)
+        # models/fcn_head.py:73-85 (smoothness is not enabled in AMD)
+        self.loss_func = unFlowLoss(_FlowLossCfg(alpha=10, ssim_sz=ssim_sz, occ_from_back=True, type="unflow", w_l1=0.15,
+                                                 w_scales=[1.0, 1.0, 1.0, 1.0, 0.0], w_sm_scales=[1.0, 0.0, 0.0, 0.0, 0.0],
+                                                 w_real_smooth=0., w_ssim=0.85, w_ternary=0.0, warp_pad="border", with_bk=True))
+        if load_flownet:
+            pth = torch.load(flow_model_path)
+            result = self.flownet.load_state_dict(pth["state_dict"], strict=False)
+            print(f"[Flownet] loaded {flow_model_path}: {result}")
+        if freeze_flownet:
+            for p in self.flownet.parameters():
+                p.requires_grad = False
+
+    def _no_convs(self, what):
+        if self.create_flownet:
+            raise RuntimeError(f"FCNHead(create_flownet=True) holds a flow network and no convs: {what} is not defined for it, "
+                               "call flow_forward(imgs, masks)")
+
+    def flow_forward(self, imgs, masks, need_whole=True):
+        """models/fcn_head.py:149-209 on ops.frame_pair, the native PWCLite and unFlowLoss.  imgs: normalised frames [B, I, 3, H, W];
+        masks: [B, I, M, h, w], or a list of the I frames' [B, M, h, w] tensors (ops.mask_softmax's frame-major output, no copy).
+        -> (flows {'seg', 'whole'}, flow_loss {'seg', 'whole'}, flows_bg, flows_fg, groups).  need_whole=False skips the loss of the
+        whole-image flows and their normalised copies: flow_loss['whole'] is 0.0 and flows['whole'] is empty."""
+        if not self.create_flownet:
+            raise RuntimeError("flow_forward needs FCNHead(create_flownet=True)")
+        I = imgs.shape[1]
+        frames = list(masks) if isinstance(masks, (list, tuple)) else [masks[:, i] for i in range(I)]
+        if len(frames) != I:
+            raise ValueError(f"{len(frames)} mask frames for {I} image frames")
+        flow_loss = {"seg": 0.0, "whole": 0.0}
+        flows = {"seg": [], "whole": []}
+        flows_bg, flows_fg, groups = [], [], []
+
+        def get_loss(flows_12, flows_21):
+            return self.loss_func([torch.cat([a, b], 1) for a, b in zip(flows_12, flows_21)], two_frame)[0]
+
+        def get_norm_flow(lis1, lis2):
+            out = []
+            for f in (lis1[0], lis2[0]):
+                h, w = f.shape[2:]
+                out.append(torch.cat([f[:, 0:1] / (h / 2.0), f[:, 1:2] / (w / 2.0)], 1))
+            return torch.cat(out, 1)
+
+        for i in range(1, I):
+            two_frame = ops.frame_pair(imgs[:, i - 1:i + 1].float(), self.flow_size)
+            res = self.flownet(two_frame, [frames[i - 1].contiguous(), frames[i].contiguous()], with_bk=True)
+            flow_loss["seg"] = flow_loss["seg"] + get_loss(res["flows_fw"], res["flows_bw"])
+            flows["seg"].append(get_norm_flow(res["flows_fw"], res["flows_bw"]))
+            if need_whole:
+                flow_loss["whole"] = flow_loss["whole"] + get_loss(res["flows_fw_all"], res["flows_bw_all"])
+                flows["whole"].append(get_norm_flow(res["flows_fw_all"], res["flows_bw_all"]))
+            flows_bg.append(-1)
+            flows_fg.append(-1)
+            groups.append(res["flows_fw_group"])
+        return flows, flow_loss, flows_bg, flows_fg, groups
+
     def transform_inputs(self, feats, tape):
         if self.input_transform == "resize_concat":
             sel = [feats[i] for i in self.in_index]
@@ -225,6 +302,7 @@ class FCNHead(nn.Module):
         return feats[self.in_index]
 
     def fwd(self, feats, tape, dist=None):
+        self._no_convs("fwd")
         mods = list(self.convs.children())
         first = None
         if self.commute_upsample and self.input_transform == "resize_concat" and len(self.in_index) == 2 \
@@ -257,5 +335,6 @@ class FCNHead(nn.Module):
     def forward(self, inputs):
         """nn.Module surface (list of NCHW maps -> NCHW logits), inference only."""
         from .layers import Tape
+        self._no_convs("forward")
         feats = [Act(ops.nchw_to_nhwc(f.contiguous().float()), needs_grad=False) for f in inputs]
         return ops.nhwc_to_nchw(self.fwd(feats, Tape(enabled=False)).t)

@@ -112,6 +112,25 @@ def stage22_model_kwargs(mask_size=(120, 214), dropout=0.1, norm="SyncBN"):
     return kw
 
 
+def amd_model_kwargs(mask_layer=5, dropout=0.1, norm="SyncBN", log_interval=1000):
+    """`model_kwargs` of configs/amd/amd.yaml:58-110 (the AMD baseline, rcf_amd.AMDModel): a ResNet-50 dilated in its last stage only,
+    the mask head on the last stage's 2048 channels, and a flow head that holds PWC-Lite (its conv settings are read and unused, as
+    in the reference)."""
+    ncfg = dict(type=norm, requires_grad=True)
+    loss = dict(type="CrossEntropyLoss", use_sigmoid=False, loss_weight=1.0)
+    return dict(
+        w_seg=1.0, mask_layer=mask_layer, log_interval=log_interval,
+        backbone2=dict(dilations=[1, 1, 1, 2], strides=[1, 2, 1, 1], type="ResNet", depth=50, num_stages=4, out_indices=[0, 1, 2, 3],
+                       norm_cfg=dict(ncfg), norm_eval=False, style="pytorch", contract_dilation=False),
+        decode_head=dict(ssim_sz=1, create_flownet=True, flow_model_path="", freeze_flownet=False, load_flownet=False,
+                         mask_layer=mask_layer, concat_input=False, dilation=6, channels=128, type="FCNHead", in_channels=2048,
+                         in_index=3, num_convs=8, dropout_ratio=0.1, num_classes=24, norm_cfg=dict(ncfg), align_corners=False,
+                         loss_decode=dict(loss)),
+        decode_head2=dict(concat_input=False, dilation=6, channels=256, type="FCNHead", in_channels=2048, in_index=3, num_convs=2,
+                          dropout_ratio=dropout, num_classes=mask_layer, norm_cfg=dict(ncfg), align_corners=False,
+                          loss_decode=dict(loss)))
+
+
 def mask_size_for(H, W):
     """spatial size after the 7x7/2 stem and the 3x3/2 max-pool."""
     h1, w1 = (H - 1) // 2 + 1, (W - 1) // 2 + 1

@@ -3,7 +3,7 @@
 // mmseg `resize` (bilinear) models/decode_head.py:157-163, models/rcf_model.py:213-220,438-442;
 // torch.cat models/decode_head.py:164; unflatten/flatten models/rcf_model.py:325.
 // PyTorch index arithmetic is reproduced exactly.
-#include "rcf_common.h"
+#include "resize_pos.h"
 
 namespace {
 
@@ -97,19 +97,7 @@ __global__ void __launch_bounds__(256) maxpool_bwd_kernel(const T *__restrict__ 
 }
 
 // ------------------------------------------------------------------------------------------- resize
-// PyTorch area_pixel_compute_source_index (UpSample.h): align_corners ? scale*dst
-//   : max(scale*(dst+0.5)-0.5, 0); scale = align ? (in-1)/(out-1) : in/out.
-__device__ __forceinline__ void src_index(int dst, float scale, int align, int in_size, int &i0, int &i1, float &l1) {
-    float s = align ? scale * dst : fmaxf(scale * (dst + 0.5f) - 0.5f, 0.f);
-    i0 = (int)s;
-    if (i0 > in_size - 1) i0 = in_size - 1;
-    i1 = i0 + (i0 < in_size - 1 ? 1 : 0);
-    l1 = s - i0;
-}
-inline float host_scale(int in, int out, int align) {
-    if (align) return out > 1 ? (float)(in - 1) / (float)(out - 1) : 0.f;
-    return (float)in / (float)out;
-}
+// src_index, host_scale and blend: resize_pos.h (shared with csrc/amd.hip)
 
 // pixel q of the border frame of thickness t of an H x W image (top strip, bottom strip, left, right; row-major each)
 __device__ __forceinline__ void frame_yx(int q, int H, int W, int t, int &y, int &x) {
@@ -139,12 +127,6 @@ struct ResizeGeom {
     float sh, sw;
     int frame;
 };
-
-// the bilinear blend, the horizontal blends of the two source rows first: ONE expression tree for every resize of the library
-// (the exact-2x kernels below share its halves between outputs)
-__device__ __forceinline__ float blend(float hy, float ly, float hx, float lx, float v00, float v01, float v10, float v11) {
-    return hy * (hx * v00 + lx * v01) + ly * (hx * v10 + lx * v11);
-}
 
 // output pixel (n, yo, xo), channels cv * V .. + V: the body of both general forward kernels
 template <typename T, int V>

@@ -54,28 +54,36 @@ class _TapeBackward(torch.autograd.Function):
         model = ctx.model
         params = [p for p in model.parameters() if p.requires_grad]
         assert len(params) == ctx.n, "the set of trainable parameters changed between forward and backward"
-        # the tape accumulates into p.grad: point every p.grad at a view of one fresh zero-filled flat buffer for the
-        # duration of the tape, hand those views to autograd, and put the user's .grad tensors back
-        sizes = [(p.numel() + 63) // 64 * 64 for p in params]
-        flat = torch.zeros(sum(sizes), dtype=torch.float32, device=params[0].device)
-        saved, views, off = [], [], 0
-        for p, n in zip(params, sizes):
-            chunk = flat[off:off + p.numel()]
-            if p.dim() == 4 and p.permute(0, 2, 3, 1).is_contiguous():      # channels_last conv weight
-                co, ci, r, s = p.shape
-                v = chunk.view(co, r, s, ci).permute(0, 3, 1, 2)
-            else:
-                v = chunk.view(p.shape)
-            saved.append(p.grad)
-            p.grad = v
-            views.append(v)
-            off += n
-        try:
-            model.run_backward(grad_out)
-        finally:
-            for p, g in zip(params, saved):
-                p.grad = g
-        return (None, None) + tuple(views)
+        return (None, None) + grads_through_flat_buffer(params, lambda: model.run_backward(grad_out))
+
+
+def grads_through_flat_buffer(params, run):
+    """What a bridge node between torch autograd and the tape hands back for its parameter inputs: `run()` accumulates into p.grad
+    (the tape does), so every p.grad points at a view of one fresh zero-filled flat buffer for the duration of `run`, those views
+    are returned for autograd's AccumulateGrad nodes, and the user's .grad tensors are put back."""
+    if not params:
+        run()
+        return ()
+    sizes = [(p.numel() + 63) // 64 * 64 for p in params]
+    flat = torch.zeros(sum(sizes), dtype=torch.float32, device=params[0].device)
+    saved, views, off = [], [], 0
+    for p, n in zip(params, sizes):
+        chunk = flat[off:off + p.numel()]
+        if p.dim() == 4 and p.permute(0, 2, 3, 1).is_contiguous():      # channels_last conv weight
+            co, ci, r, s = p.shape
+            v = chunk.view(co, r, s, ci).permute(0, 3, 1, 2)
+        else:
+            v = chunk.view(p.shape)
+        saved.append(p.grad)
+        p.grad = v
+        views.append(v)
+        off += n
+    try:
+        run()
+    finally:
+        for p, g in zip(params, saved):
+            p.grad = g
+    return tuple(views)
 
 
 @torch.no_grad()
@@ -134,7 +142,92 @@ def momentum_update_param_and_buffer(src, dest, m):
     ops.weights_changed(dest)            # only `dest` was written: the source's cached operands stay valid
 
 
-class RCFModel(nn.Module):
+class SegModelBase(nn.Module):
+    """What RCFModel and AMDModel share around their forward passes: the output directories, the weight-cache invalidation of
+    train(), the data-parallel context, the image plumbing and the evaluation side effects (the 2x grid JPEG and the
+    `pred_seg_*.png` exports, models/rcf_model.py:241-273,296-315 == models/amd/amd_model.py:120-152,166-190)."""
+
+    def _init_dirs(self, args):
+        self.args = args
+        ckpt = getattr(args, "checkpoints_dir", ".")
+        self.save_dir = os.path.join(ckpt, "saved")
+        self.save_dir_eval = os.path.join(ckpt, getattr(args, "saved_eval_dir_name", "saved_eval"))
+        self.save_dir_eval_export = os.path.join(ckpt, getattr(args, "saved_eval_export_dir_name", "saved_eval_export"))
+
+    def train(self, mode=True):
+        if bool(mode) != self.training:                     # a transition (trainers call train() at the top of every step)
+            ops.weights_changed()
+        return super().train(mode)
+
+    def _dist(self):
+        if self.dist is None:
+            self.dist = DistCtx()
+        return self.dist
+
+    def _images_nhwc(self, imgs):
+        B, I, C3, H, W = imgs.shape
+        x = imgs.reshape(B * I, C3, H, W).contiguous().float()
+        if not x.is_cuda:
+            raise RuntimeError(f"{type(self).__name__} (HIP) needs the batch on the GPU: there is no CPU fallback")
+        if self._act_dtype in ops.H16 and layers.SCHED.bf16_stem:
+            # 16-bit step: the stem conv takes 16-bit operands like every other conv (torch autocast casts conv1's input too)
+            return Act(ops.cast(ops.nchw_to_nhwc(x, 8), self._act_dtype), needs_grad=False)
+        return Act(ops.nchw_to_nhwc(x, 4), needs_grad=False)
+
+    def resize(self, x, size):
+        """mmseg.ops.resize(bilinear, align_corners=self.align_corners) on NCHW (rcf_model.py:208-214)"""
+        return ops.resize_nchw(x.contiguous().float(), tuple(size), self.align_corners)
+
+    def save_eval_visualizations(self, tosave, paths, seq_ids, seq_names, name="eval", train_iter=0):
+        """rcf_model.py:241-251: one JPEG of the whole batch grid, named after sample 0"""
+        if _rank() != 0:
+            return
+        frame_id = paths[0][0].split("/")[-1][:-4]
+        fn = f"{self.save_dir_eval}/{name}_{seq_names[0]}_{_item(seq_ids[0])}_{frame_id}_{train_iter:07}.jpg"
+        try:
+            save_image(tosave, fn)
+        except Exception as e:                                 # the reference logs and carries on
+            print(f"Error in saving: {fn} {e}")
+
+    def export_seg(self, tosave, paths, seq_ids, seq_names, name="eval", train_iter=0, subdir=""):
+        """rcf_model.py:253-267: one PNG per sample of the batch"""
+        if _rank() != 0:
+            return
+        sub = subdir + "/" if subdir else ""
+        for i, (path, seq_name, _seq_id) in enumerate(zip(paths[0], seq_names, seq_ids)):
+            frame_id = path.split("/")[-1][:-4]
+            fn = f"{self.save_dir_eval_export}/{sub}{name}_{seq_name}_{frame_id}_{train_iter:07}.png"
+            try:
+                save_image(tosave[i], fn)
+            except Exception as e:
+                print(f"Error in saving: {fn} {e}")
+
+    def export_all_seg(self, tosave, paths, seq_ids, seq_names, name="eval", train_iter=0):
+        for idx, item in enumerate(tosave):                    # rcf_model.py:269-273
+            self.export_seg(item, paths, seq_ids, seq_names, name, train_iter, subdir=str(idx))
+
+    def _eval_outputs(self, imgs, pred_masks, seq_ids, seq_names, paths, return_pred_vis_list=False):
+        """the tail of forward_eval: pred_masks [B,C,h,w] of the current frame; with args.eval_save the 2x visualisation grid (and
+        with args.eval_export the object-channel / all-channel PNGs) are written"""
+        want_save = bool(getattr(self.args, "eval_save", False))
+        if not (want_save or return_pred_vis_list):
+            return pred_masks
+        h, w = pred_masks.shape[-2:]
+        img0 = (self.resize(imgs[:, 0], (h * 2, w * 2)) + 2.0) / 4.0
+        vis = [self.resize(pred_masks[:, i:i + 1].contiguous(), (h * 2, w * 2)).repeat(1, 3, 1, 1)
+               for i in range(min(self.mask_layer, pred_masks.shape[1]))]
+        if want_save:
+            self.save_eval_visualizations(torch.cat([img0] + vis, 2), paths, seq_ids, seq_names, train_iter=self.train_iter)
+            if getattr(self.args, "eval_export", False):
+                if getattr(self.args, "export_all_seg", False):
+                    self.export_all_seg(vis, paths, seq_ids, seq_names, name="pred_seg", train_iter=self.train_iter)
+                else:
+                    self.export_seg(vis[self.args.object_channel], paths, seq_ids, seq_names, name="pred_seg",
+                                    train_iter=self.train_iter)
+        return (pred_masks, vis) if return_pred_vis_list else pred_masks
+
+
+class RCFModel(SegModelBase):
     def __init__(self, args, backbone2, decode_head, decode_head2, decode_head3, compactness_head=None,
                  crf_head=None, crf_use_ema=False, ema_m=0.999, w_seg=2.0, w_sharpen=0, t_sharpen=0.25, w_entropy=0,
                  w_compactness=0, w_pl=0, pl_pos_weight=1., pl_neg_weight=1., pl_mask_pos_th=0.35, w_crf=0,
@@ -142,11 +235,10 @@ class RCFModel(nn.Module):
                  test_cfg=None, align_corners=False, mask_size=(48, 48), log_interval=50, freeze_backbone=False,
                  object_aware_sharpening=False, separate_residual=False, allow_mask_resize=False):
         super().__init__()
-        self.args = args
-        ckpt = getattr(args, "checkpoints_dir", ".")
-        self.save_dir = os.path.join(ckpt, "saved")
-        self.save_dir_eval = os.path.join(ckpt, getattr(args, "saved_eval_dir_name", "saved_eval"))
-        self.save_dir_eval_export = os.path.join(ckpt, getattr(args, "saved_eval_export_dir_name", "saved_eval_export"))
+        self._init_dirs(args)
+        for name, cfg in (("decode_head2", decode_head2), ("decode_head3", decode_head3)):
+            if cfg.get("create_flownet"):           # before anything is built: RCF has no use for a flow network there
+                raise NotImplementedError(f"RCFModel: {name} with create_flownet=True is the AMD baseline's flow head (rcf_amd.AMDModel)")
 
         def build(cfg, **extra):
             # like the reference (rcf_model.py:161-197) this pops 'type'/'create_ema' from the caller's dict
@@ -209,20 +301,10 @@ class RCFModel(nn.Module):
     # train() keeps the reference's semantics (it has no override): the EMA copies are set to eval mode once, at
     # construction (models/rcf_model.py:171,187); `model.train()` -- Lightning calls it on the whole module tree --
     # switches them to training mode with everything else, so under main.py the stage-2.1 teacher runs with batch
-    # statistics.  The override below only invalidates the cached weight operands (fp16 planes, bf16 copies, ranges):
+    # statistics.  The override (SegModelBase.train) only invalidates the cached weight operands (fp16 planes, bf16 copies, ranges):
     # they are keyed by (data_ptr, _version, epoch) and an in-place write through `.data` bumps none of those, so every
     # mode SWITCH (not the train() call a trainer repeats every step) and every load_state_dict starts from fresh operands.  Anything else that writes parameters through
     # `.data` / raw pointers after a forward must call `rcf_amd.ops.weights_changed()` itself.
-
-    def train(self, mode=True):
-        if bool(mode) != self.training:                     # a transition (trainers call train() at the top of every step)
-            ops.weights_changed()
-        return super().train(mode)
-
-    def _dist(self):
-        if self.dist is None:
-            self.dist = DistCtx()
-        return self.dist
 
     def _teacher_dist(self):
         """the EMA teacher's SyncBN exchanges on their OWN communicator: its forward is enqueued (on the side stream)
@@ -258,16 +340,6 @@ class RCFModel(nn.Module):
         # of THIS forward pass: every Tape it makes carries it
         self._act_dtype = {"fp32": torch.float32, "bf16": torch.bfloat16, "fp16": torch.float16}[p]
         return p
-
-    def _images_nhwc(self, imgs):
-        B, I, C3, H, W = imgs.shape
-        x = imgs.reshape(B * I, C3, H, W).contiguous().float()
-        if not x.is_cuda:
-            raise RuntimeError("RCFModel (HIP) needs the batch on the GPU: there is no CPU fallback")
-        if self._act_dtype in ops.H16 and layers.SCHED.bf16_stem:
-            # 16-bit step: the stem conv takes 16-bit operands like every other conv (torch autocast casts conv1's input too)
-            return Act(ops.cast(ops.nchw_to_nhwc(x, 8), self._act_dtype), needs_grad=False)
-        return Act(ops.nchw_to_nhwc(x, 4), needs_grad=False)
 
     def run_backward(self, grad_out=None):
         """Backward of the last forward_train: fills param.grad (accumulating)."""
@@ -366,38 +438,6 @@ class RCFModel(nn.Module):
         return ops.resize_nchw(crf.view(B, I, H, W).contiguous(), self.mask_size, self.align_corners)
 
     # ------------------------------------------------------------------ eval forward
-    def resize(self, x, size):
-        """mmseg.ops.resize(bilinear, align_corners=self.align_corners) on NCHW (rcf_model.py:208-214)"""
-        return ops.resize_nchw(x.contiguous().float(), tuple(size), self.align_corners)
-
-    def save_eval_visualizations(self, tosave, paths, seq_ids, seq_names, name="eval", train_iter=0):
-        """rcf_model.py:241-251: one JPEG of the whole batch grid, named after sample 0"""
-        if _rank() != 0:
-            return
-        frame_id = paths[0][0].split("/")[-1][:-4]
-        fn = f"{self.save_dir_eval}/{name}_{seq_names[0]}_{_item(seq_ids[0])}_{frame_id}_{train_iter:07}.jpg"
-        try:
-            save_image(tosave, fn)
-        except Exception as e:                                 # the reference logs and carries on
-            print(f"Error in saving: {fn} {e}")
-
-    def export_seg(self, tosave, paths, seq_ids, seq_names, name="eval", train_iter=0, subdir=""):
-        """rcf_model.py:253-267: one PNG per sample of the batch"""
-        if _rank() != 0:
-            return
-        sub = subdir + "/" if subdir else ""
-        for i, (path, seq_name, _seq_id) in enumerate(zip(paths[0], seq_names, seq_ids)):
-            frame_id = path.split("/")[-1][:-4]
-            fn = f"{self.save_dir_eval_export}/{sub}{name}_{seq_name}_{frame_id}_{train_iter:07}.png"
-            try:
-                save_image(tosave[i], fn)
-            except Exception as e:
-                print(f"Error in saving: {fn} {e}")
-
-    def export_all_seg(self, tosave, paths, seq_ids, seq_names, name="eval", train_iter=0):
-        for idx, item in enumerate(tosave):                    # rcf_model.py:269-273
-            self.export_seg(item, paths, seq_ids, seq_names, name, train_iter, subdir=str(idx))
-
     @torch.no_grad()
     def forward_eval(self, imgs, seq_ids=None, seq_names=None, paths=None, return_pred_vis_list=False):
         """rcf_model.py:275-320: softmax masks of the current frame [B,C,h,w]; with args.eval_save the 2x
@@ -411,22 +451,7 @@ class RCFModel(nn.Module):
         else:
             logits = self.decode_head2.fwd(self.backbone2.fwd(img, t), t)
         pred_masks = self.decode_head.softmax_masks(logits.t, B, I)[:, 0]
-        want_save = bool(getattr(self.args, "eval_save", False))
-        if not (want_save or return_pred_vis_list):
-            return pred_masks
-        h, w = pred_masks.shape[-2:]
-        img0 = (self.resize(imgs[:, 0], (h * 2, w * 2)) + 2.0) / 4.0
-        vis = [self.resize(pred_masks[:, i:i + 1].contiguous(), (h * 2, w * 2)).repeat(1, 3, 1, 1)
-               for i in range(min(self.mask_layer, pred_masks.shape[1]))]
-        if want_save:
-            self.save_eval_visualizations(torch.cat([img0] + vis, 2), paths, seq_ids, seq_names, train_iter=self.train_iter)
-            if getattr(self.args, "eval_export", False):
-                if getattr(self.args, "export_all_seg", False):
-                    self.export_all_seg(vis, paths, seq_ids, seq_names, name="pred_seg", train_iter=self.train_iter)
-                else:
-                    self.export_seg(vis[self.args.object_channel], paths, seq_ids, seq_names, name="pred_seg",
-                                    train_iter=self.train_iter)
-        return (pred_masks, vis) if return_pred_vis_list else pred_masks
+        return self._eval_outputs(imgs, pred_masks, seq_ids, seq_names, paths, return_pred_vis_list)
 
     def forward(self, x, return_pred_vis_list=False):
         imgs = torch.stack(x["imgs"], dim=1)

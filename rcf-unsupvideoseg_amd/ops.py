@@ -1291,6 +1291,55 @@ def pwc_unpack(dbuf, c0, D):
     return dcorr, dflow
 
 
+# ------------------------------------------------------------------------------- AMDModel's seam (csrc/amd.hip)
+def _mask_operands(logits, M):
+    _pwc_operands(logits)
+    if logits.dim() != 4 or not 1 <= M <= logits.shape[3] or logits.shape[3] not in (4, 8):
+        raise _lib.RcfHipError(f"logits must be NHWC [B I, h, w, 4 or 8] with the first M channels live: {tuple(logits.shape)}, M = {M}")
+
+
+def mask_softmax(logits, B, I, M):
+    """NHWC logits [B I, h, w, Cp] of images n = b I + i -> softmax masks over the first M channels, frame-major and planar
+    [I, B, M, h, w]: out[i] is the contiguous [B, M, h, w] mask of frame i"""
+    _mask_operands(logits, M)
+    N, h, w, Cp = logits.shape
+    if N != B * I:
+        raise _lib.RcfHipError(f"{N} images are not {B} samples of {I} frames")
+    masks = torch.empty((I, B, M, h, w), dtype=torch.float32, device=logits.device)
+    call("rcf_amd_mask_softmax_fwd_f32", _p(logits), pitch_of(logits), _p(masks), I, B, M, Cp, h * w, _stream())
+    return masks
+
+
+def mask_softmax_bwd(masks, dmasks, Cp, out=None):
+    """masks [I, B, M, h, w] (mask_softmax's output), dmasks: I gradients [B, M, h, w], None = zeros -> dlogits NHWC [B I, h, w, Cp]
+    (a given `out` may be wider-pitched; its channels from Cp up are left alone)"""
+    _pwc_operands(masks, out, *dmasks)
+    I, B, M, h, w = masks.shape
+    if len(dmasks) != I or any(d is not None and tuple(d.shape) != (B, M, h, w) for d in dmasks) or not masks.is_contiguous():
+        raise _lib.RcfHipError(f"dmasks must hold {I} gradients [B, M, h, w] (or None) for contiguous masks {tuple(masks.shape)}")
+    keep = [None if d is None else d.contiguous() for d in dmasks]
+    if out is None:
+        out = torch.empty((B * I, h, w, Cp), dtype=torch.float32, device=masks.device)
+    if tuple(out.shape) != (B * I, h, w, Cp):
+        raise _lib.RcfHipError(f"out must be NHWC {(B * I, h, w, Cp)}: {tuple(out.shape)}")
+    ptrs = (c_void_p * I)(*[None if d is None else d.data_ptr() for d in keep])
+    call("rcf_amd_mask_softmax_bwd_f32", _p(masks), ptrs, _p(out), pitch_of(out), I, B, M, Cp, h * w, _stream())
+    return out
+
+
+def frame_pair(frames, size):
+    """normalised frames [B, 2, 3, H, W] -> two_frame [B, 6, Ho, Wo]: (x std + mean) / 255 per channel, then bilinear with
+    align_corners=True (models/fcn_head.py:160-170), one launch"""
+    _pwc_operands(frames)
+    if frames.dim() != 5 or tuple(frames.shape[1:3]) != (2, 3):
+        raise _lib.RcfHipError(f"frames must be [B, 2, 3, H, W]: {tuple(frames.shape)}")
+    frames = frames.contiguous()
+    B, _, _, H, W = frames.shape
+    out = torch.empty((B, 6, int(size[0]), int(size[1])), dtype=torch.float32, device=frames.device)
+    call("rcf_amd_frame_pair_f32", _p(frames), _p(out), B, H, W, int(size[0]), int(size[1]), _stream())
+    return out
+
+
 # ------------------------------------------------------------------------------- optimiser
 def adam_step(param, grad, exp_avg, exp_avg_sq, lr, step, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0,
               grad_scale=1.0):

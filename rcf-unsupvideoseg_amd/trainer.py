@@ -301,6 +301,8 @@ class Trainer:
         self.fp.zero_grad()
         with torch.no_grad():
             losses = self.model(batch)
+        if torch.is_tensor(losses):                         # AMDModel returns its one loss as a tensor (models/amd/amd_model.py:266)
+            losses = {"loss": losses}
         self._pending, self._done = [], set()
         scale = self.scaler.scale if self.scaler is not None else 1.0
         self.model.run_backward(scale if self.scaler is not None else None)
