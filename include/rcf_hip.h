@@ -989,6 +989,31 @@ int rcf_amd_mask_softmax_bwd_f32(const float *masks, const float *const *dmasks,
  * positions of rcf_resize_bilinear_nchw_f32.  Sizes 1 .. 2^14, 0 < B <= 65535. */
 int rcf_amd_frame_pair_f32(const float *frames, float *out, int B, int Hi, int Wi, int Ho, int Wo, void *stream);
 
+/* ---- Middlebury flow colours for the training visualisation grids (flow_vis.flow_to_color as models/rcf_model.py:222-234 and
+ * models/amd/amd_model.py:213-262 call it, once per sample, frame and flow kind on the host; csrc/flowvis.hip).
+ * n_images flow images of h x w float32, coloured each by its own maximum radius, in at most two launches whatever n_images is: one
+ * where h w <= rcf_flow_color_geometry(0), otherwise a maximum launch (atomic max on the bit pattern of the non-negative radius: the
+ * same bits on every call) and a colour launch; no host synchronisation.
+ * Layouts are in ELEMENTS of the tensor's own type.  Image n = g group + k (0 <= k < group) starts at g image + k member; channel c
+ * (flow: u, v; colours: the three planes), row y and column x add c channel + y row + x col.  So the channel slices [:, :2] / [:, 2:] of
+ * a [B, 4, h, w] tensor and an [h, w, 2] array (channel 1, col 2) are read in place, and the planes may go into a window of a wider
+ * canvas: `out` points at the window's first element and nothing outside the h x w x 3 elements the layout names is written.  With
+ * group > 1 the images of one grid row (the flow kinds of a sample) may sit `member` apart inside a canvas image.  Strides >= 0, col >= 1.
+ * out_type: RCF_FLOW_COLOR_U8 bytes 0 .. 255, RCF_FLOW_COLOR_F32 byte / 255 rounded once to float32 (the reference's flow_color / 255.0).
+ * convert_to_bgr swaps planes 0 and 2.  clip < 0: none; otherwise u, v <- clamp(., 0, clip) (np.clip(flow, 0, clip_flow)).
+ * The package's rad > 1 branch (col * 0.75), dead in exact arithmetic, is never taken.  Non-finite flows (or magnitudes whose squares
+ * overflow) make their image's colours meaningless but written in full and equal from call to call; other images are unaffected.
+ * 1 <= h, w <= 2^14, 1 <= n_images <= 2^20, n_images % group == 0.  workspace: rcf_flow_color_workspace_bytes() bytes, 4-byte aligned,
+ * zeroed in-stream by the call (0 bytes, may be NULL, in the one-launch form; the query returns 0 for a refused shape too).
+ * rcf_flow_color_geometry(which): 0 the largest image (pixels) of the one-launch form, 1 pixels per workgroup of the two-launch form. */
+#define RCF_FLOW_COLOR_U8 0
+#define RCF_FLOW_COLOR_F32 1
+typedef struct { long image, member, channel, row, col; } rcf_flow_layout;
+int rcf_flow_color_geometry(int which);
+size_t rcf_flow_color_workspace_bytes(int n_images, int group, int h, int w);
+int rcf_flow_color_f32(const float *flow, const rcf_flow_layout *src, void *out, const rcf_flow_layout *dst, int out_type, int n_images,
+                       int group, int h, int w, int convert_to_bgr, float clip, void *workspace, size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -6,7 +6,7 @@ helpers of utils/warp_utils.py and a `torchcrf_cpp`-shaped `crf_soft` / `crf_har
 """
 __version__ = "0.1.0"
 
-from . import _lib, data_pipeline, davis, evaluate, maa, ncut, offline, ops, semantic, synth, vit  # noqa: F401
+from . import _lib, data_pipeline, davis, evaluate, flowvis, maa, ncut, offline, ops, semantic, synth, vit  # noqa: F401
 from .backbone import FCNHead, ResNet  # noqa: F401
 from .correlation import Correlation  # noqa: F401
 from .evaluate import Evaluator  # noqa: F401

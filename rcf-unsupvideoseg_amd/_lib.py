@@ -99,7 +99,15 @@ class FlowHeadCfg(ctypes.Structure):
                 ("sharpen_mode", c_int)]
 
 
+class FlowLayout(ctypes.Structure):
+    """mirror of rcf_flow_layout: element strides of (image group, member of a group, channel, row, column)"""
+    _fields_ = [(n, c_long) for n in ("image", "member", "channel", "row", "col")]
+
+
+FLOW_COLOR_U8, FLOW_COLOR_F32 = 0, 1      # rcf_flow_color_f32's out_type
+
 P = c_void_p
+_FL = ctypes.POINTER(FlowLayout)
 _CS = ctypes.POINTER(ConvShape)
 _FH = ctypes.POINTER(FlowHeadCfg)
 _CR = ctypes.POINTER(ConvRegion)
@@ -217,6 +225,9 @@ PROTOS = {
     "rcf_amd_mask_softmax_fwd_f32": (c_int, [P, c_int, P, c_int, c_int, c_int, c_int, c_int, P]),
     "rcf_amd_mask_softmax_bwd_f32": (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, P]),
     "rcf_amd_frame_pair_f32": (c_int, [P, P, c_int, c_int, c_int, c_int, c_int, P]),
+    "rcf_flow_color_geometry": (c_int, [c_int]),
+    "rcf_flow_color_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "rcf_flow_color_f32": (c_int, [P, _FL, P, _FL, c_int, c_int, c_int, c_int, c_int, c_int, c_float, P, c_size_t, P]),
     "rcf_crf_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "rcf_crf_soft": (c_int, [P, P, c_int, c_int, c_int, c_float, c_float, c_float, c_float, c_float, c_int, P, P, P,
                              P, c_size_t, P]),

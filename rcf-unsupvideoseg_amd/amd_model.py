@@ -10,12 +10,13 @@ so that each frame's mask is the contiguous tensor PWCLite.forward takes); its b
 gradient (ops.mask_softmax_bwd), runs the tape and hands the parameters' gradients back to autograd -- so `loss.backward()` reaches
 every parameter, torch DDP's hooks see each one once, and the flow network's parameters get theirs from torch autograd.
 
-float32 only: the flow network has no 16-bit path.  Not reproduced: the flow-colour training visualisations every `log_interval`
-steps (amd_model.py:213-264), as for RCFModel -- so the whole-image flows' loss and the resized predicted flows, which only they
-read, are not computed (flow_forward(need_whole=False))."""
+float32 only: the flow network has no 16-bit path.  The training visualisations every `log_interval` steps (amd_model.py:213-264)
+are written as for RCFModel (SegModelBase.train_vis_due, flowvis.py): masks, frame, segment flow and whole-image flow of every
+sample, the flows coloured on the device.  Only such a step computes the whole-image flows and their loss, which nothing else reads
+(flow_forward(need_whole=True)); every other step skips them."""
 import torch
 
-from . import ops
+from . import flowvis, ops
 from .layers import Tape
 from .model import REGISTRY, SegModelBase, grads_through_flat_buffer
 
@@ -90,13 +91,29 @@ class AMDModel(SegModelBase):
         logits = self.decode_head2.fwd(self.backbone2.fwd(self._images_nhwc(imgs), tape, dist), tape, dist)     # Act [B*I,h,w,Cp]
         self.last_logits = logits.t
         params = [p for m in (self.backbone2, self.decode_head2) for p in m.parameters() if p.requires_grad]
+        vis_due = self.train_vis_due(paths)
         with torch.enable_grad():        # also under a trainer's no_grad: run_backward differentiates the stored loss
             masks = _MaskBridge.apply(logits, tape, B, I, self.mask_layer, *params)
-            _, flow_loss, _, _, _ = self.decode_head.flow_forward(imgs, list(masks), need_whole=False)
+            flows, flow_loss, _, _, _ = self.decode_head.flow_forward(imgs, list(masks), need_whole=vis_due)
             loss = flow_loss["seg"] * self.w_seg
         self._loss = loss
+        if vis_due:
+            self._write_train_vis(imgs, masks, flows, seq_ids, seq_names, paths)
         self.train_iter += 1
         return loss if torch.is_grad_enabled() else loss.detach()
+
+    @torch.no_grad()
+    def _write_train_vis(self, imgs, masks, flows, seq_ids, seq_names, paths):
+        """amd_model.py:207-264: the M mask panels, the frame, the segment and the whole-image flow (normalised, resized to the mask
+        shape; frame 0 from the first two channels, frame 1 from the last two) of every sample as one JPEG"""
+        B, I = imgs.shape[:2]
+        h, w = masks[0].shape[-2:]
+        assert len(flows["seg"]) == 1 and len(flows["whole"]) == 1
+        kinds = flowvis.AMD_FLOW_KINDS
+        fl = torch.stack([self.resize(flows[k][0].detach(), (h, w)) for k in kinds], 1)               # [B, K, 4, h, w]
+        fl = fl.view(B, len(kinds), I, 2, h, w).permute(2, 0, 1, 3, 4, 5).contiguous().view(I * B, len(kinds), 2, h, w)
+        tosave = self.train_grid(torch.stack([m.detach() for m in masks]), imgs, fl, kinds)
+        self.save_train_visualizations(tosave, paths, seq_ids, seq_names)
 
     # ------------------------------------------------------------------ eval forward (amd_model.py:155-192)
     @torch.no_grad()

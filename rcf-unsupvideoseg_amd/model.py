@@ -5,8 +5,11 @@ registry by `type` name, same state-dict keys, same return contract (dict of 0-d
 training mode whose 'loss' entry supports `.backward()`, softmax masks [B,C,h,w] in eval mode).
 
 The evaluation side effects are reproduced (eval JPEG, `pred_seg_*.png` export, :241-273,:296-315, through
-export.py's stand-in for torchvision.utils.save_image).  Not reproduced: the flow-colour training
-visualisations every `log_interval` steps (:456-462,:562-608; they need flow_vis and are off the arithmetic path).
+export.py's stand-in for torchvision.utils.save_image), and so are the training ones: every `log_interval` steps the grid
+`saved/train_iter{:07d}_{seq}_{id}_{frame}_img_pred_recons.jpg` (:456-462,:562-608) -- masks, frames, the flows in Middlebury
+colours, pseudo-label masks -- with the flows coloured on the device (ops.flow_color instead of flow_vis on the host, flowvis.py),
+and with log_interval == 1 the `saved_train_export/*.pth` dump.  A step writes them when it is due, the batch came with `paths`,
+`saved/` exists (main.py creates it) and args.train_save is not False (SegModelBase.train_vis_due); otherwise nothing is launched.
 """
 import os
 from copy import deepcopy
@@ -14,7 +17,7 @@ from copy import deepcopy
 import torch
 import torch.nn as nn
 
-from . import ops
+from . import flowvis, ops
 from .export import save_image
 from .backbone import FCNHead, ResNet
 from .crf import CRFHead
@@ -144,8 +147,9 @@ def momentum_update_param_and_buffer(src, dest, m):
 
 class SegModelBase(nn.Module):
     """What RCFModel and AMDModel share around their forward passes: the output directories, the weight-cache invalidation of
-    train(), the data-parallel context, the image plumbing and the evaluation side effects (the 2x grid JPEG and the
-    `pred_seg_*.png` exports, models/rcf_model.py:241-273,296-315 == models/amd/amd_model.py:120-152,166-190)."""
+    train(), the data-parallel context, the image plumbing, the evaluation side effects (the 2x grid JPEG and the
+    `pred_seg_*.png` exports, models/rcf_model.py:241-273,296-315 == models/amd/amd_model.py:120-152,166-190) and the training
+    visualisation grid (its gate, the mask / frame / flow-colour panels, the file name and the save)."""
 
     def _init_dirs(self, args):
         self.args = args
@@ -225,6 +229,48 @@ class SegModelBase(nn.Module):
                     self.export_seg(vis[self.args.object_channel], paths, seq_ids, seq_names, name="pred_seg",
                                     train_iter=self.train_iter)
         return (pred_masks, vis) if return_pred_vis_list else pred_masks
+
+    # ------------------------------------------------------------------ training visualisations
+    def let_tensor_vis(self, t, setmax=False):
+        """rcf_model.py:222-234: one flow image [1, 2, h, w] -> its Middlebury colours [1, 3, h, w], float32 levels 0 .. 255, on
+        the device (the reference goes through the host and flow_vis once per sample, frame and flow kind)."""
+        t = t.clone()
+        if setmax:
+            _th_ = 0.2
+            t[:, 0, 0, 0] = _th_
+            t[:, 1, 0, 0] = _th_
+            assert torch.max(t[:, 0, :, :]) == _th_
+            assert torch.max(t[:, 1, :, :]) == _th_
+        return ops.flow_color(t.float()).float()
+
+    def train_vis_due(self, paths):
+        """whether THIS training step writes its grid: every log_interval steps (train_iter before its increment), when the batch
+        came with paths, `saved/` exists under the checkpoint directory (main.py creates it) and args.train_save is not False"""
+        return (self.train_iter % self.log_interval == 0 and paths is not None and bool(getattr(self.args, "train_save", True))
+                and os.path.isdir(self.save_dir))
+
+    @torch.no_grad()
+    def train_grid(self, masks, imgs, flows, kinds, pl=None):
+        """The grid of rcf_model.py:456-462,562-595 == amd_model.py:213-257 as one canvas [I B, 3, P h, w] (flowvis.grid_panels).
+        masks [I, B, M, h, w] (a view will do), imgs [B, I, 3, H, W], flows [I B, K, 2, h, w] frame-major (row i B + b: sample b,
+        frame i), pl [I, B, h, w] or None."""
+        I, B, M, h, w = masks.shape
+        frames = self.resize(imgs.detach().transpose(0, 1).reshape(I * B, *imgs.shape[2:]), (h, w))
+        frames = (frames + 2.0) / 4.0                       # "an approximate un-normalization for visualization"
+        panels = flowvis.grid_panels(M, kinds, pl is not None)
+        canvas = flowvis.new_canvas(I, B, panels, h, w, masks.device)
+        self.last_train_grid = flowvis.fill_grid(canvas, panels, masks, frames, flows, pl)     # (tests look at it)
+        return self.last_train_grid
+
+    def save_train_visualizations(self, tosave, paths, seq_ids, seq_names):
+        """rcf_model.py:580-608: one JPEG of the whole batch grid, named after sample 0; every rank writes (the names differ)"""
+        frame_id = paths[0][0].split("/")[-1][:-4]
+        fn = "{}/train_iter{:07d}_{}_{}_{}_img_pred_recons.jpg".format(self.save_dir, self.train_iter, seq_names[0],
+                                                                      _item(seq_ids[0]), frame_id)
+        try:
+            save_image(tosave, fn)
+        except Exception:
+            print(f"Error in saving: {fn}")
 
 
 class RCFModel(SegModelBase):
@@ -352,8 +398,9 @@ class RCFModel(SegModelBase):
             tape.backward()
 
     # ------------------------------------------------------------------ training forward
-    def forward_train(self, imgs, gt_fw_flows, gt_bw_flows, pl_masks=None):
+    def forward_train(self, imgs, gt_fw_flows, gt_bw_flows, pl_masks=None, seq_ids=None, seq_names=None, paths=None):
         B, I = imgs.shape[:2]
+        vis_due = self.train_vis_due(paths)
         dist = self._dist()
         self._select_precision()
         tape = Tape(on_mark=self.grad_ready_hook, act_dtype=self._act_dtype)
@@ -405,7 +452,7 @@ class RCFModel(SegModelBase):
                 extra["crf_masks"] = self._crf_targets(img, imgs, logits, B, I)
         losses, seed = self.decode_head.loss_and_grads(
             self, logits, res, gfw.view(B, nf, 2, *self.mask_size), gbw.view(B, nf, 2, *self.mask_size), extra, B, I,
-            act_dtype=self._act_dtype)
+            want_flows=vis_due, act_dtype=self._act_dtype)
         self._seed_backward = seed
         self._tape = tape
         self.last_targets = extra        # the pl / crf targets at mask size that entered the loss (tests look at them)
@@ -414,10 +461,37 @@ class RCFModel(SegModelBase):
             momentum_update_param_and_buffer(self.backbone2, self.backbone2_ema, self.ema_m)
         if self.decode_head2_ema is not None:
             momentum_update_param_and_buffer(self.decode_head2, self.decode_head2_ema, self.ema_m)
+        if vis_due:
+            self._write_train_vis(imgs, seq_ids, seq_names, paths, gfw.view(B, nf, 2, *self.mask_size),
+                                  gbw.view(B, nf, 2, *self.mask_size), extra.get("pl_masks"))
         self.train_iter += 1
         if torch.is_grad_enabled():
             losses["loss"] = _TapeBackward.apply(losses["loss"], self, *[p for p in self.parameters() if p.requires_grad])
         return losses
+
+    @torch.no_grad()
+    def _write_train_vis(self, imgs, seq_ids, seq_names, paths, gfw, gbw, pl):
+        """rcf_model.py:456-462,533-608 from the head's flows of THIS step (FlowAggregationHead.last_flows, want_flows=True): the
+        visualisation flows of FlowAggregationHead.forward -- divided by (h / 2, w / 2); their resize to the mask shape is the
+        identity -- in the reference's order, frame 0 from the first two channels and frame 1 from the last two."""
+        B, I = imgs.shape[:2]
+        head, (h, w) = self.decode_head, self.mask_size
+        f = head.last_flows
+        kinds = flowvis.rcf_flow_kinds(head.free_residual_with_affine)
+        flows = torch.stack([f[k] for k in kinds], 1)                                   # [B I (n = 2 b + d), K, 2, h, w]
+        flows = flows.view(B, I, len(kinds), 2, h, w).transpose(0, 1).contiguous().view(I * B, len(kinds), 2, h, w)
+        s = torch.full((1, 1, 2, 1, 1), h / 2.0, dtype=torch.float32, device=flows.device)
+        s[:, :, 1] = w / 2.0
+        flows /= s
+        masks = f["masks"].view(B, I, self.mask_layer, h, w).transpose(0, 1)
+        tosave = self.train_grid(masks, imgs, flows, kinds, None if pl is None else pl.transpose(0, 1))
+        if self.log_interval == 1:                                                      # rcf_model.py:599-602
+            if self.train_iter == 0:
+                os.makedirs(f"{self.save_dir}_train_export", exist_ok=False)
+            frame_id = paths[0][0].split("/")[-1][:-4]
+            torch.save([imgs, seq_ids, seq_names, paths, gfw, gbw, pl, tosave],
+                       f"{self.save_dir}_train_export/{seq_names[0]}_{frame_id}.pth")
+        self.save_train_visualizations(tosave, paths, seq_ids, seq_names)
 
     @torch.no_grad()
     def _crf_targets(self, img_act, imgs, logits, B, I):
@@ -460,5 +534,6 @@ class RCFModel(SegModelBase):
             if self.training:
                 pl = torch.stack(x["pl_masks"], dim=1) if self.w_pl > 0 else None
                 return self.forward_train(imgs, torch.stack(x["gt_fw_flows"], dim=1),
-                                          torch.stack(x["gt_bw_flows"], dim=1), pl)
+                                          torch.stack(x["gt_bw_flows"], dim=1), pl, x.get("seq_ids"), x.get("seq_names"),
+                                          x.get("paths"))
             return self.forward_eval(imgs, x.get("seq_ids"), x.get("seq_names"), x.get("paths"), return_pred_vis_list)

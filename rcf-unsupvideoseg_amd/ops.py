@@ -1340,6 +1340,51 @@ def frame_pair(frames, size):
     return out
 
 
+# ------------------------------------------------------------------------------- flow colours (csrc/flowvis.hip)
+def flow_color_geometry():
+    """(largest image, in pixels, of the one-launch form; pixels per workgroup of the two-launch form)"""
+    lib = _lib.load()
+    return lib.rcf_flow_color_geometry(0), lib.rcf_flow_color_geometry(1)
+
+
+def _flow_layout(t):
+    """element strides (image group, member, channel, row, column) of a [G, K, C, h, w] view; a dimension of one element gets 0"""
+    return _lib.FlowLayout(*[int(t.stride(i)) if t.shape[i] > 1 else 0 for i in range(4)], int(t.stride(4)) if t.shape[4] > 1 else 1)
+
+
+def flow_color(flows, out=None, out_dtype=torch.uint8, convert_to_bgr=False, clip_flow=None):
+    """Middlebury colours (flow_vis.flow_to_color) of flow images [..., 2, h, w] -- [2, h, w], [N, 2, h, w] or [G, K, 2, h, w] -- each
+    normalised by its own maximum, in at most two launches for all of them.  Any strided float32 view is read in place (channel
+    slices of a [B, 4, h, w] tensor, a permuted [h, w, 2] array).  out: a uint8 or float32 view [..., 3, h, w] with the same leading
+    dimensions, e.g. a window of a canvas; created (contiguous, `out_dtype`) when None.  float32 holds byte / 255."""
+    _need_cuda(flows, out)
+    if flows.dtype != torch.float32:
+        raise _lib.RcfHipError(f"flow_color takes float32 flows, not {flows.dtype}")
+    if not 3 <= flows.dim() <= 5 or flows.shape[-3] != 2 or flows.numel() == 0:
+        raise _lib.RcfHipError(f"flows must be [..., 2, h, w] with at most two leading dimensions: {tuple(flows.shape)}")
+    lead, (h, w) = tuple(flows.shape[:-3]), flows.shape[-2:]
+    if clip_flow is not None and not float(clip_flow) >= 0:
+        raise _lib.RcfHipError(f"clip_flow must be None or >= 0: {clip_flow}")
+    if out is None:
+        if out_dtype not in (torch.uint8, torch.float32):
+            raise _lib.RcfHipError(f"flow_color writes uint8 or float32, not {out_dtype}")
+        out = torch.empty(lead + (3, h, w), dtype=out_dtype, device=flows.device)
+    if out.dtype not in (torch.uint8, torch.float32) or tuple(out.shape) != lead + (3, h, w) or out.device != flows.device:
+        raise _lib.RcfHipError(f"out must be uint8 or float32 {lead + (3, h, w)} on {flows.device}: {out.dtype} {tuple(out.shape)}")
+    f5 = flows[(None,) * (5 - flows.dim())]
+    o5 = out[(None,) * (5 - out.dim())]
+    G, K = f5.shape[:2]
+    if any(s < 0 for s in f5.stride() + o5.stride()):
+        raise _lib.RcfHipError("flow_color takes views with non-negative strides")
+    src, dst = _flow_layout(f5), _flow_layout(o5)
+    need = _lib.load().rcf_flow_color_workspace_bytes(G * K, K, h, w)
+    ws = workspace(need, flows.device) if need else None
+    call("rcf_flow_color_f32", _p(flows), byref(src), _p(out), byref(dst),
+         _lib.FLOW_COLOR_U8 if out.dtype == torch.uint8 else _lib.FLOW_COLOR_F32, G * K, K, h, w, int(bool(convert_to_bgr)),
+         -1.0 if clip_flow is None else float(clip_flow), _p(ws), need, _stream())
+    return out
+
+
 # ------------------------------------------------------------------------------- optimiser
 def adam_step(param, grad, exp_avg, exp_avg_sq, lr, step, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0,
               grad_scale=1.0):
