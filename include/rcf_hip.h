@@ -1014,6 +1014,40 @@ size_t rcf_flow_color_workspace_bytes(int n_images, int group, int h, int w);
 int rcf_flow_color_f32(const float *flow, const rcf_flow_layout *src, void *out, const rcf_flow_layout *dst, int out_type, int n_images,
                        int group, int h, int w, int convert_to_bgr, float clip, void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- Evaluation export: every 8-bit RGB panel of a batch in ONE launch (csrc/export.hip; the image side of forward_eval,
+ * models/rcf_model.py:241-273,296-315: resize + repeat + save_image's rounding once per sample and channel).
+ * Sources.  masks [B][C][h][w] float32 (sample b at b mask_sample ELEMENTS, its C planes contiguous) and frames [B][3][H][W] float32
+ * (sample b at b frame_sample elements: a [B, I, 3, H, W] batch's frame 0 is read in place).
+ * A panel is Ho x Wo pixels of 3 bytes: its source resized with rcf_resize_bilinear_nchw_f32's arithmetic (the float32 source positions
+ * and blend of that entry point, `align_corners` as given), a frame then mapped (v + 2) / 4, and rounded as torchvision.utils.save_image
+ * rounds: t = v * 255, t = t + 0.5 (two float32 roundings), clamp to [0, 255], truncate.  A mask's byte goes to all three colours.
+ * NaN is written as 0; +inf and every level above 255 as 255, -inf and every level below 0 as 0.  (An infinite source value gives a NaN
+ * level where one of its blend weights is 0.)  Bytes are the same from call to call; panels of other planes are unaffected.
+ * Destinations.  n_dst (1 .. rcf_export_geometry(3)) layouts, all written by the same launch; strides in BYTES, all >= 0, pixel >= 3.
+ * Layout d holds n_slots x B panels: slot j of sample b starts at
+ *     base + y row + x pixel + (b / per_row) image_row + (b % per_row) image + j slot,
+ * row r and pixel c of it at + r row + c pixel.  source[j] is the mask channel (0 .. C - 1) of slot j, or RCF_EXPORT_FRAME.
+ * So {image = Ho Wo 3, per_row >= B, slot = B Ho Wo 3, row = Wo 3, pixel = 3} is a contiguous [n_slots][B][Ho][Wo][3] buffer (all
+ * channels, or one), and {x, y = the grid's padding, image / image_row = a grid cell's width / height, slot = Ho row, per_row = 8} the
+ * windows of make_grid's canvas with the panels of a sample stacked downwards.  `bytes` is the size of the buffer behind base: a layout
+ * whose last panel would end beyond it is refused; nothing outside the panels is written (the caller keeps panels from overlapping).
+ * Where pixel == 3 and a run of 4 pixels starts on a dword boundary its 12 bytes are one store; otherwise bytes up to the boundary,
+ * whole dwords, and a byte tail.  1 <= B <= 65535, at most 65535 panels per call, sizes 1 .. 2^14.  frames / masks may be NULL when no
+ * slot names them.  rcf_export_geometry(which): 0 pixels per thread and run, 1 threads per workgroup, 2 runs per thread (a workgroup
+ * takes 0 x 1 x 2 pixels of one panel, runs numbered row-major), 3 the largest n_dst; 0 otherwise. */
+#define RCF_EXPORT_MAX_SLOTS 16
+#define RCF_EXPORT_FRAME (-1)
+typedef struct {
+    unsigned char *base;
+    long bytes;
+    long image, image_row, slot, row, pixel;
+    int x, y, per_row, n_slots;
+    int source[RCF_EXPORT_MAX_SLOTS];
+} rcf_export_layout;
+int rcf_export_geometry(int which);
+int rcf_export_panels_u8(const float *masks, long mask_sample, int C, int h, int w, const float *frames, long frame_sample, int H, int W,
+                         const rcf_export_layout *dst, int n_dst, int B, int Ho, int Wo, int align_corners, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -19,3 +19,5 @@ from .ops import occu_mask_bidirection as get_occu_mask_bidirection  # noqa: F40
 from .pwc_lite import PWCLite  # noqa: F401
 from .trainer import Trainer, poly_lr_factor  # noqa: F401
 from .unflow_loss import unFlowLoss  # noqa: F401
+from . import export, export_driver  # noqa: F401,E402
+from .export import MaskExporter  # noqa: F401

@@ -105,6 +105,14 @@ class FlowLayout(ctypes.Structure):
 
 
 FLOW_COLOR_U8, FLOW_COLOR_F32 = 0, 1      # rcf_flow_color_f32's out_type
+EXPORT_MAX_SLOTS, EXPORT_FRAME = 16, -1   # RCF_EXPORT_MAX_SLOTS, RCF_EXPORT_FRAME
+
+
+class ExportLayout(ctypes.Structure):
+    """mirror of rcf_export_layout: one destination of rcf_export_panels_u8 (byte strides)"""
+    _fields_ = [("base", c_void_p), ("bytes", c_long)] + [(n, c_long) for n in ("image", "image_row", "slot", "row", "pixel")] + \
+               [(n, c_int) for n in ("x", "y", "per_row", "n_slots")] + [("source", c_int * EXPORT_MAX_SLOTS)]
+
 
 P = c_void_p
 _FL = ctypes.POINTER(FlowLayout)
@@ -228,6 +236,9 @@ PROTOS = {
     "rcf_flow_color_geometry": (c_int, [c_int]),
     "rcf_flow_color_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
     "rcf_flow_color_f32": (c_int, [P, _FL, P, _FL, c_int, c_int, c_int, c_int, c_int, c_int, c_float, P, c_size_t, P]),
+    "rcf_export_geometry": (c_int, [c_int]),
+    "rcf_export_panels_u8": (c_int, [P, c_long, c_int, c_int, c_int, P, c_long, c_int, c_int, ctypes.POINTER(ExportLayout), c_int, c_int,
+                                     c_int, c_int, c_int, P]),
     "rcf_crf_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "rcf_crf_soft": (c_int, [P, P, c_int, c_int, c_int, c_float, c_float, c_float, c_float, c_float, c_int, P, P, P,
                              P, c_size_t, P]),

@@ -182,12 +182,23 @@ class SegModelBase(nn.Module):
         """mmseg.ops.resize(bilinear, align_corners=self.align_corners) on NCHW (rcf_model.py:208-214)"""
         return ops.resize_nchw(x.contiguous().float(), tuple(size), self.align_corners)
 
+    exporter = None         # an export.MaskExporter: _eval_outputs then writes its files through it (one kernel call per batch)
+
+    def eval_grid_name(self, paths, seq_ids, seq_names, name="eval", train_iter=0):
+        frame_id = paths[0][0].split("/")[-1][:-4]
+        return f"{self.save_dir_eval}/{name}_{seq_names[0]}_{_item(seq_ids[0])}_{frame_id}_{train_iter:07}.jpg"
+
+    def export_seg_names(self, paths, seq_ids, seq_names, name="eval", train_iter=0, subdir=""):
+        """the files export_seg writes, one per sample"""
+        sub = subdir + "/" if subdir else ""
+        return [f"{self.save_dir_eval_export}/{sub}{name}_{seq_name}_{path.split('/')[-1][:-4]}_{train_iter:07}.png"
+                for path, seq_name, _seq_id in zip(paths[0], seq_names, seq_ids)]
+
     def save_eval_visualizations(self, tosave, paths, seq_ids, seq_names, name="eval", train_iter=0):
         """rcf_model.py:241-251: one JPEG of the whole batch grid, named after sample 0"""
         if _rank() != 0:
             return
-        frame_id = paths[0][0].split("/")[-1][:-4]
-        fn = f"{self.save_dir_eval}/{name}_{seq_names[0]}_{_item(seq_ids[0])}_{frame_id}_{train_iter:07}.jpg"
+        fn = self.eval_grid_name(paths, seq_ids, seq_names, name, train_iter)
         try:
             save_image(tosave, fn)
         except Exception as e:                                 # the reference logs and carries on
@@ -197,10 +208,7 @@ class SegModelBase(nn.Module):
         """rcf_model.py:253-267: one PNG per sample of the batch"""
         if _rank() != 0:
             return
-        sub = subdir + "/" if subdir else ""
-        for i, (path, seq_name, _seq_id) in enumerate(zip(paths[0], seq_names, seq_ids)):
-            frame_id = path.split("/")[-1][:-4]
-            fn = f"{self.save_dir_eval_export}/{sub}{name}_{seq_name}_{frame_id}_{train_iter:07}.png"
+        for i, fn in enumerate(self.export_seg_names(paths, seq_ids, seq_names, name, train_iter, subdir)):
             try:
                 save_image(tosave[i], fn)
             except Exception as e:
@@ -217,6 +225,8 @@ class SegModelBase(nn.Module):
         if not (want_save or return_pred_vis_list):
             return pred_masks
         h, w = pred_masks.shape[-2:]
+        if self.exporter is not None:
+            return self._eval_outputs_exporter(imgs, pred_masks, seq_ids, seq_names, paths, want_save, return_pred_vis_list)
         img0 = (self.resize(imgs[:, 0], (h * 2, w * 2)) + 2.0) / 4.0
         vis = [self.resize(pred_masks[:, i:i + 1].contiguous(), (h * 2, w * 2)).repeat(1, 3, 1, 1)
                for i in range(min(self.mask_layer, pred_masks.shape[1]))]
@@ -229,6 +239,29 @@ class SegModelBase(nn.Module):
                     self.export_seg(vis[self.args.object_channel], paths, seq_ids, seq_names, name="pred_seg",
                                     train_iter=self.train_iter)
         return (pred_masks, vis) if return_pred_vis_list else pred_masks
+
+    def _eval_outputs_exporter(self, imgs, pred_masks, seq_ids, seq_names, paths, want_save, return_pred_vis_list):
+        """_eval_outputs with self.exporter attached: the same files with the same bytes from ONE kernel call and one enqueue per
+        batch (export.MaskExporter); `vis` is only built when the caller asks for it"""
+        h, w = pred_masks.shape[-2:]
+        size, nvis = (h * 2, w * 2), min(self.mask_layer, pred_masks.shape[1])
+        if want_save and _rank() == 0:
+            channels, names = [], []
+            if getattr(self.args, "eval_export", False):
+                if getattr(self.args, "export_all_seg", False):
+                    channels = list(range(nvis))
+                    names = [self.export_seg_names(paths, seq_ids, seq_names, "pred_seg", self.train_iter, subdir=str(c)) for c in channels]
+                else:
+                    channels = [range(nvis)[self.args.object_channel]]
+                    names = [self.export_seg_names(paths, seq_ids, seq_names, "pred_seg", self.train_iter)]
+                if any(len(n) != pred_masks.shape[0] for n in names):
+                    raise ValueError("the exporter needs a path, a sequence name and a sequence id for every sample of the batch")
+            self.exporter.submit(pred_masks, imgs[:, 0], size, self.align_corners, channels, names,
+                                 [ops.EXPORT_FRAME] + list(range(nvis)), self.eval_grid_name(paths, seq_ids, seq_names, train_iter=self.train_iter))
+        if not return_pred_vis_list:
+            return pred_masks
+        vis = [self.resize(pred_masks[:, i:i + 1].contiguous(), size).repeat(1, 3, 1, 1) for i in range(nvis)]
+        return pred_masks, vis
 
     # ------------------------------------------------------------------ training visualisations
     def let_tensor_vis(self, t, setmax=False):

@@ -1385,6 +1385,72 @@ def flow_color(flows, out=None, out_dtype=torch.uint8, convert_to_bgr=False, cli
     return out
 
 
+# ------------------------------------------------------------------------------- evaluation export (csrc/export.hip)
+EXPORT_FRAME = _lib.EXPORT_FRAME
+
+
+def export_geometry():
+    """(pixels per run, threads per workgroup, runs per thread, destinations per call) of rcf_export_panels_u8"""
+    lib = _lib.load()
+    return tuple(lib.rcf_export_geometry(i) for i in range(4))
+
+
+def export_layout(buf, sources, *, image, slot, row, image_row=0, pixel=3, x=0, y=0, per_row=1 << 30):
+    """One destination of export_panels_u8 in a uint8 device tensor `buf` (any shape; addressed from its first byte, strides in
+    bytes): panel (slot j, sample b) starts at y row + x pixel + (b // per_row) image_row + (b % per_row) image + j slot.
+    sources[j]: the mask channel of slot j or EXPORT_FRAME."""
+    if buf.dtype != torch.uint8 or not buf.is_contiguous():
+        raise _lib.RcfHipError("export_layout takes a contiguous uint8 buffer")
+    if not 1 <= len(sources) <= _lib.EXPORT_MAX_SLOTS:
+        raise _lib.RcfHipError(f"1 .. {_lib.EXPORT_MAX_SLOTS} slots per layout: {len(sources)}")
+    l = _lib.ExportLayout(buf.data_ptr(), buf.numel(), int(image), int(image_row), int(slot), int(row), int(pixel), int(x), int(y),
+                          int(min(per_row, 1 << 30)), len(sources))
+    for j, s in enumerate(sources):
+        l.source[j] = int(s)
+    l._keep = buf                                        # the buffer outlives the struct that names it
+    return l
+
+
+def export_contiguous_layout(buf, sources):
+    """`buf` uint8 [len(sources), B, Ho, Wo, 3] contiguous: the PNG arrays of the selected channels"""
+    S, B, Ho, Wo, three = buf.shape
+    assert S == len(sources) and three == 3
+    return export_layout(buf, sources, image=Ho * Wo * 3, slot=B * Ho * Wo * 3, row=Wo * 3)
+
+
+def export_panels_u8(masks, frames, layouts, size, align_corners=False):
+    """Every panel of a batch as 8-bit RGB in one launch: masks [B, C, h, w] float32 planes and / or normalised frames [B, 3, H, W]
+    ((v + 2) / 4), resized to `size` like resize_nchw and rounded like export.to_uint8_hwc, into the windows `layouts` name
+    (export_layout / export_contiguous_layout; at most export_geometry()[3] of them).  Either source may be None when no slot
+    names it.  No host synchronisation."""
+    _need_cuda(masks, frames)
+    B = None
+    C = h = w = H = W = 0
+    ms = fs = 0
+    if masks is not None:
+        if masks.dim() != 4:
+            raise _lib.RcfHipError(f"masks must be [B, C, h, w]: {tuple(masks.shape)}")
+        masks = masks.float().contiguous()
+        B, C, h, w = masks.shape
+        ms = C * h * w
+    if frames is not None:
+        if frames.dim() != 4 or frames.shape[1] != 3:
+            raise _lib.RcfHipError(f"frames must be [B, 3, H, W]: {tuple(frames.shape)}")
+        frames = frames.float()
+        H, W = frames.shape[-2:]
+        if frames.stride()[1:] != (H * W, W, 1) or (frames.shape[0] > 1 and frames.stride(0) < 3 * H * W):
+            frames = frames.contiguous()                 # (a [B, I, 3, H, W] batch's frame 0 is read in place)
+        if B is not None and frames.shape[0] != B:
+            raise _lib.RcfHipError("masks and frames must hold the same samples")
+        B = frames.shape[0]
+        fs = frames.stride(0) if B > 1 else 3 * H * W
+    if B is None or not layouts:
+        raise _lib.RcfHipError("export_panels_u8 needs a source and a destination")
+    arr = (_lib.ExportLayout * len(layouts))(*layouts)
+    call("rcf_export_panels_u8", _p(masks), ms, C, h, w, _p(frames), fs, H, W, arr, len(layouts), B, int(size[0]), int(size[1]),
+         int(bool(align_corners)), _stream())
+
+
 # ------------------------------------------------------------------------------- optimiser
 def adam_step(param, grad, exp_avg, exp_avg_sq, lr, step, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0,
               grad_scale=1.0):
