@@ -50,6 +50,44 @@ static inline int set_region(P &p, const rcf_conv_region *r, int N, int H, int W
     return 0;
 }
 
+// The GEMM view of a forward (x -> y) or data-gradient (dy -> dx) launch (P = IgemmParams, ConvParams): rows = the pixels of y / dx,
+// columns = its channels, K = (tap, source channel); source coordinate t = y * up + off + r * step, valid iff t >= 0, t % div == 0
+// and t / div inside the source.  Everything but the operands, the region and the epilogue.
+template <class P>
+static inline void fill_gemm_view(P &p, const rcf_conv_shape *s, bool dgrad) {
+    p.flags = s->flags;
+    p.S = s->S;
+    if (dgrad) {
+        p.Ncol = s->Cin; p.K = s->R * s->S * s->Cout;
+        p.Ho = s->H; p.Wo = s->W; p.Hs = s->Ho; p.Ws = s->Wo; p.Cs = s->Cout;
+        p.up = 1; p.off = s->pad; p.step = -s->dil; p.div = s->stride;
+        p.a_pitch = s->y_pitch; p.a_img_stride = (long)s->Ho * s->Wo * s->y_pitch; p.y_pitch = s->x_pitch;
+    } else {
+        p.Ncol = s->Cout; p.K = s->R * s->S * s->Cin;
+        p.Ho = s->Ho; p.Wo = s->Wo; p.Hs = s->H; p.Ws = s->W; p.Cs = s->Cin;
+        p.up = s->stride; p.off = -s->pad; p.step = s->dil; p.div = 1;
+        p.a_pitch = s->x_pitch; p.a_img_stride = (long)s->H * s->W * s->x_pitch; p.y_pitch = s->y_pitch;
+    }
+}
+
+// The K order of a forward / data-gradient launch (rcf_common.h rcf_kchunk) into the launch parameters or the plan: the channel
+// chunk width (Cs = the natural order: one chunk), taps * width, and their magics.  width: RCF_KCHUNK_F32 / RCF_KCHUNK_BF16
+template <class P>
+static inline void fill_korder(P &p, unsigned flags, int taps, int Cs, int width) {
+    const int kch = rcf_kchunk(korder_chunked(flags), taps, Cs, width);
+    p.kch = kch ? kch : Cs;
+    p.rsch = taps * p.kch;
+    p.kch_magic = magic_of(p.kch);
+    p.rsch_magic = magic_of(p.rsch);
+}
+
+// 32-bit arithmetic of the forward / data-gradient kernels: the K walk's divisions by magic (kend = K + one K-step: the
+// look-ahead runs one step past the end) and the descriptor offsets of the activation operand -- the images one row tile can
+// touch must lie within 2 GiB of the first one.  rr = rows per image, esize = bytes per element
+static inline bool conv_offsets_fit(int kend, int rsch, int rr, long a_img_stride, int esize) {
+    return (long)kend * rsch < (1L << 32) && (256 / (long)rr + 2) * a_img_stride * esize < (1L << 31);
+}
+
 // Split K (the M pixels) of a weight gradient over `c` workgroups per tile, c in 1..hi, on `slots` resident workgroups.  Cost
 // model in microseconds: rounds(c) x pixels per workgroup x time per pixel (px_us) + the fixed-order reduction, which reads c
 // copies of the weight gradient (wbytes each, ~2 bytes/us/1e6 effective).  Small weights on many pixels (layer1) want hundreds

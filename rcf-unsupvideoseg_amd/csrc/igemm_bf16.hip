@@ -24,7 +24,6 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
-constexpr unsigned OOB = 0x80000000u;      // byte offset beyond every descriptor's num_records: loads return 0
 constexpr int BKT = 32;                    // K-step (bf16 elements)
 
 struct ConvParams {
@@ -77,36 +76,7 @@ __device__ __forceinline__ float keep_if(float v, unsigned long long mask) {
     return out;
 }
 
-__device__ __forceinline__ void region_yx(int pix, int ry0, int rx0, int rh, int rw, int t, int &y, int &x) {
-    if (t <= 0) {
-        const int yr = pix / rw;
-        y = yr + ry0;
-        x = pix - yr * rw + rx0;
-        return;
-    }
-    const int strip = t * rw;
-    if (pix < 2 * strip) {
-        const int bottom = pix >= strip;
-        const int q = pix - (bottom ? strip : 0);
-        const int yr = q / rw;
-        y = ry0 + yr + (bottom ? rh - t : 0);
-        x = rx0 + q - yr * rw;
-    } else {
-        int q = pix - 2 * strip;
-        const int side = t * (rh - 2 * t);
-        const int right = q >= side;
-        q -= right ? side : 0;
-        const int yr = q / t;
-        y = ry0 + t + yr;
-        x = rx0 + q - yr * t + (right ? rw - t : 0);
-    }
-}
-
-__device__ __forceinline__ int fast_div(int k, unsigned magic) { return magic ? (int)__umulhi((unsigned)k, magic) : k; }
-// the same without a branch on the (uniform) divisor-is-one case: keeps a K-step's address arithmetic in one basic block
-__device__ __forceinline__ int fast_div_nb(int k, unsigned magic) {
-    return (int)(__umulhi((unsigned)k, magic) + ((unsigned)k & (magic ? 0u : ~0u)));
-}
+#include "conv_rows.h"                     // what the forward / data-gradient kernels of this file and of igemm_conv.hip share
 
 __device__ __forceinline__ u32x2 pack4(const f32x4 v) {
     const bf16x2 a = __builtin_convertvector(f32x2{v[0], v[1]}, bf16x2), b = __builtin_convertvector(f32x2{v[2], v[3]}, bf16x2);
@@ -139,20 +109,20 @@ __device__ __forceinline__ void mma_step(const char *__restrict__ As, const char
 // forward / data gradient.  Workgroup = WM x WN waves, each owning MR x NR accumulator tiles of 32x32.
 // DGRAD only names the instantiation (profiles tell forward and data-gradient launches apart).
 // OBF: bf16 output (16-byte stores after a half-wave exchange), else fp32 output.
-// SCHED (DMA only): 1 = the steady-state K-step is one basic block with the LDS-DMA pieces placed among the MFMAs (the
-// default), 0 = pieces issued ahead of the K-step's MFMAs (A/B reference, rcf_conv_bf16_set_tile(4)).
-// DMA: both operands go from global memory STRAIGHT into LDS (buffer_load ... lds, 16 bytes per lane: no staging
-// registers, no ds_write pass); three LDS stages, the loads of K-step t+2 are issued before the MFMAs of step t and
-// stay in flight across the one barrier per step (counted s_waitcnt vmcnt).  The LDS image of a wave instruction is
-// lane-linear (1 KB = 16 rows x 64 B), so the XOR swizzle of the 16-byte chunks is applied to the SOURCE address.
+// Both operands go from global memory STRAIGHT into LDS (buffer_load ... lds, 16 bytes per lane: no staging registers, no
+// ds_write pass): three LDS stages, the loads of K-step t+2 are issued among the MFMAs of step t and stay in flight across
+// the one barrier per step (counted s_waitcnt vmcnt).  The LDS image of a wave instruction is lane-linear (1 KB = 16 rows
+// x 64 B), so the XOR swizzle of the 16-byte chunks is applied to the SOURCE address.
+// DMA, NST, SCHED: the register-staged path, other stage counts and the pieces-ahead-of-the-MFMAs loop they once selected are
+// gone; every launch passes <true, 3, 1>, and the parameters stay because profiles and tools name instances by the full list.
 template <int MR, int NR, int WM, int WN, bool STRIDED, bool DGRAD, bool OBF, bool DMA = false, int NST = 3, int SCHED = 0, int EP = 0>
 __global__ void __launch_bounds__(64 * WM * WN, (WM * WN == 4 && NST == 3) ? 2 : 1) conv_bf16_kernel(ConvParams p) {
     static_assert(EP == 0 || OBF, "the fused epilogues write bf16");
+    static_assert(DMA && NST == 3 && SCHED == 1, "one K loop: LDS-DMA, three stages, pieces among the MFMAs");
     constexpr int NT = 64 * WM * WN;
     constexpr int BM = 32 * MR * WM, BN = 32 * NR * WN;
     constexpr int PA = BM * 64, PB = BN * 64, STAGE = PA + PB;
-    constexpr int NSTAGE = DMA ? NST : 2;
-    __shared__ __attribute__((aligned(16))) char smem[NSTAGE * STAGE];
+    __shared__ __attribute__((aligned(16))) char smem[NST * STAGE];
 
     // XCD aware (as igemm_conv_x3_kernel): ids b, b + 8, .. walk the column tiles of one row tile, each XCD its own contiguous
     // range of row tiles; p.colmap: each XCD its own column tiles of every row tile (rcf_common.h rcf_conv_tile)
@@ -181,40 +151,24 @@ __global__ void __launch_bounds__(64 * WM * WN, (WM * WN == 4 && NST == 3) ? 2 :
     constexpr int A_PASS = BM / ROWS, B_PASS = BN / ROWS;
     static_assert(A_PASS >= 1 && B_PASS >= 1, "tile smaller than one loader pass");
     const int arow = tid >> 2;
-    // register-staged path: this thread loads source chunk kq and stores it at position kq ^ swizzle; DMA path: the
-    // thread's LDS position IS tid & 3, so it loads source chunk (tid & 3) ^ swizzle
-    const int kq = DMA ? ((tid & 3) ^ ((arow >> 2) & 3)) : (tid & 3);
-    const int st_off = arow * 64 + ((kq ^ ((arow >> 2) & 3)) << 4);      // + ROWS*64 per pass (ROWS % 16 == 0)
+    const int kq = (tid & 3) ^ ((arow >> 2) & 3);     // the thread's LDS position IS tid & 3, so it loads source chunk (tid & 3) ^ swizzle
 
     const int HoWo = p.rr;
     const int n_first = m0 / HoWo;
     const __amdgpu_buffer_rsrc_t rsA = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<bf16_t *>(p.A + (long)n_first * p.a_img_stride), 0, (int)OOB, 0x00020000);
+        const_cast<bf16_t *>(p.A + (long)n_first * p.a_img_stride), 0, (int)CONV_OOB, 0x00020000);
     const __amdgpu_buffer_rsrc_t rsB =
         __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t *>(p.Bw), 0, p.b_bytes, 0x00020000);
 
     int abase[A_PASS], ay[A_PASS], ax[A_PASS];
 #pragma unroll
-    for (int i = 0; i < A_PASS; ++i) {
-        const int m = m0 + arow + ROWS * i;
-        if (m < p.M) {
-            const int n = m / HoWo;
-            int y, x;
-            region_yx(m - n * HoWo, p.ry0, p.rx0, p.rh, p.rw, p.rband, y, x);
-            ay[i] = y * p.up + p.off;
-            ax[i] = x * p.up + p.off;
-            abase[i] = (n - n_first) * (int)p.a_img_stride + (STRIDED ? 0 : (ay[i] * p.Ws + ax[i]) * p.a_pitch);
-        } else {
-            abase[i] = 0;
-            ay[i] = -(1 << 28);
-            ax[i] = -(1 << 28);
-        }
-    }
+    for (int i = 0; i < A_PASS; ++i)
+        conv_row_origin<STRIDED>(p, m0 + arow + ROWS * i, p.M, n_first, RCF_REGION_ROWMAJOR, ay[i], ax[i], abase[i]);
     unsigned bbase[B_PASS];   // byte offset of the weight row inside a K-step's block (out of range for columns past Ncol)
 #pragma unroll
     for (int i = 0; i < B_PASS; ++i) {
         const int j = n0 + arow + ROWS * i;
-        bbase[i] = j < p.Ncol ? (unsigned)j * 64u + (unsigned)kq * 16u : OOB;
+        bbase[i] = j < p.Ncol ? (unsigned)j * 64u + (unsigned)kq * 16u : CONV_OOB;
     }
     f32x16 acc[MR][NR];
 #pragma unroll
@@ -226,191 +180,83 @@ __global__ void __launch_bounds__(64 * WM * WN, (WM * WN == 4 && NST == 3) ? 2 :
     const int arow0 = wm * 32 * MR, brow0 = wn * 32 * NR;
     const int KT = (p.K + BKT - 1) / BKT;
 
-    // byte offset of this thread's 16-byte chunk of A for K-step kt, row pass i (bit 31 set = out of range: zeros)
-    auto a_offset = [&](int kt, int i, int tapoff, int c, bool kv, int dy, int dx) -> unsigned {
-        int ty = ay[i] + dy, tx = ax[i] + dx;
-        int v, off;
-        if (STRIDED) {
-            v = (int)kv & (int)(ty >= 0) & (int)(tx >= 0) & (int)(ty % p.div == 0) & (int)(tx % p.div == 0);
-            ty /= p.div;
-            tx /= p.div;
-            v &= (int)(ty < p.Hs) & (int)(tx < p.Ws);
-            off = abase[i] + (ty * p.Ws + tx) * p.a_pitch + c;
-        } else {
-            v = (int)kv & (int)((unsigned)ty < (unsigned)p.Hs) & (int)((unsigned)tx < (unsigned)p.Ws);
-            off = abase[i] + tapoff;
-        }
-        return (((unsigned)off * 2u) & ~OOB) | ((unsigned)(v - 1) & OOB);
-    };
-
-    if constexpr (DMA) {
-        // wave-uniform LDS destinations: pass i of wave w covers rows [ROWS i + 16 w, + 16) = 1 KB
-        const int wrow = __builtin_amdgcn_readfirstlane(wave) * 16 * 64;
-        auto issue = [&](int kt, int stage) {
-            char *As = smem + stage * STAGE + wrow;
-            char *Bs = As + PA;
-            const int k = kt * BKT + kq * 8;
-            const bool kv = k < p.K;
-            // position k of the K loop = (channel chunk q, tap rs, channel inside the chunk); natural order: one chunk of Cs
-            const int q = SCHED != 0 ? fast_div_nb(k, p.rsch_magic) : fast_div(k, p.rsch_magic);
-            const int rem = k - q * p.rsch;
-            const int rs = SCHED != 0 ? fast_div_nb(rem, p.kch_magic) : fast_div(rem, p.kch_magic);
-            const int c = q * p.kch + (rem - rs * p.kch);
-            const int r = SCHED != 0 ? fast_div_nb(rs, p.s_magic) : fast_div(rs, p.s_magic);
-            const int s = rs - r * p.S;
-            const int dy = r * p.step, dx = s * p.step;
-            const int tapoff = (dy * p.Ws + dx) * p.a_pitch + c;
-            const unsigned kb = (unsigned)kt * (unsigned)p.Ncol * 64u;
-#pragma unroll
-            for (int i = 0; i < B_PASS; ++i)
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(rsB, (__attribute__((address_space(3))) void *)(Bs + i * ROWS * 64), 16,
-                                                         (int)(bbase[i] + kb), 0, 0, 0);
-#pragma unroll
-            for (int i = 0; i < A_PASS; ++i)
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(rsA, (__attribute__((address_space(3))) void *)(As + i * ROWS * 64), 16,
-                                                         (int)a_offset(kt, i, tapoff, c, kv, dy, dx), 0, 0, 0);
-        };
-        constexpr int NLD = A_PASS + B_PASS;              // LDS-DMA instructions per thread per K-step
-        constexpr int AHEAD = NST - 1;                    // K-steps in flight beyond the one being multiplied
-        // wait until the loads of step `kt + 1` have landed: those of the later steps already issued stay in flight
-        auto wait_next = [&](int kt) {
-            const int later = min(KT - 1, kt + AHEAD) - (kt + 1);       // steps issued beyond kt + 1
-            if (later >= 2) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * NLD) : "memory");
-            else if (later == 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NLD) : "memory");
-            else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        };
-#pragma unroll
-        for (int i = 0; i < AHEAD; ++i)
-            if (i < KT) issue(i, i);
-        wait_next(-1);
-        __builtin_amdgcn_s_barrier();
-        int st = 0;                                       // stage of K-step kt
-        if constexpr (SCHED != 0) {
-            // steady state as ONE basic block (unconditional issue, constant wait count) so that the scheduler may place
-            // the LDS-DMA pieces among the MFMAs; the last AHEAD steps, which issue nothing, follow
-            int kt = 0;
-            for (; kt + AHEAD < KT; ++kt) {
-                const int stn = st + AHEAD >= NST ? st + AHEAD - NST : st + AHEAD;
-                const char *As = smem + st * STAGE;
-                mma_step<MR, NR>(As, As + PA, arow0, brow0, lane, acc);
-                issue(kt + AHEAD, stn);       // in program order BEHIND the fragment reads (LDS write after LDS reads)
-                {
-                    // both halves' fragments first, then one LDS-DMA piece behind each of the first MFMAs: a piece's issue
-                    // (tens of cycles) runs under the matrix pipe's work instead of ahead of it
-                    __builtin_amdgcn_sched_group_barrier(0x100, 2 * (MR + NR), 0);
-#pragma unroll
-                    for (int i = 0; i < NLD; ++i) {
-                        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                        __builtin_amdgcn_sched_group_barrier(0x010, 1, 0);
-                    }
-                    __builtin_amdgcn_sched_group_barrier(0x008, 2 * MR * NR - NLD, 0);
-                }
-                // the MFMAs may sink below the barrier (registers only); the fragment reads may not: the next step's
-                // pieces overwrite this stage
-                asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"((AHEAD - 1) * NLD) : "memory");
-                __builtin_amdgcn_s_barrier();
-                st = st == NST - 1 ? 0 : st + 1;
-            }
-            for (; kt < KT; ++kt) {
-                const char *As = smem + st * STAGE;
-                mma_step<MR, NR>(As, As + PA, arow0, brow0, lane, acc);
-                wait_next(kt);
-                __builtin_amdgcn_s_barrier();
-                st = st == NST - 1 ? 0 : st + 1;
-            }
-        } else {
-        for (int kt = 0; kt < KT; ++kt) {
-            // stage (st + AHEAD) % NST was read a step ago: free since the last barrier
-            const int stn = st + AHEAD >= NST ? st + AHEAD - NST : st + AHEAD;
-            if (kt + AHEAD < KT) issue(kt + AHEAD, stn);
-            const char *As = smem + st * STAGE;
-            mma_step<MR, NR>(As, As + PA, arow0, brow0, lane, acc);
-            wait_next(kt);
-            __builtin_amdgcn_s_barrier();
-            st = st == NST - 1 ? 0 : st + 1;
-        }
-        }
-    } else {
-    // A (activations) comes from HBM: its loads run TWO K-steps ahead (two register sets); B (weights, L2) one step ahead
-    u32x4 ra[2][A_PASS], rb[B_PASS];
-
-    auto load_a = [&](int kt, u32x4 (&dst)[A_PASS]) {
+    // wave-uniform LDS destinations: pass i of wave w covers rows [ROWS i + 16 w, + 16) = 1 KB
+    const int wrow = __builtin_amdgcn_readfirstlane(wave) * 16 * 64;
+    auto issue = [&](int kt, int stage) {
+        char *As = smem + stage * STAGE + wrow;
+        char *Bs = As + PA;
         const int k = kt * BKT + kq * 8;
         const bool kv = k < p.K;
-        const int q = fast_div(k, p.rsch_magic);
-        const int rem = k - q * p.rsch;
-        const int rs = fast_div(rem, p.kch_magic);
-        const int c = q * p.kch + (rem - rs * p.kch);
-        const int r = fast_div(rs, p.s_magic);
-        const int s = rs - r * p.S;
-        const int dy = r * p.step, dx = s * p.step;
-        const int tapoff = (dy * p.Ws + dx) * p.a_pitch + c;
-#pragma unroll
-        for (int i = 0; i < A_PASS; ++i)
-            dst[i] = __builtin_amdgcn_raw_buffer_load_b128(rsA, (int)a_offset(kt, i, tapoff, c, kv, dy, dx), 0, 0);
-    };
-    auto load_b = [&](int kt) {
+        int c, dy, dx;
+        const int rs = conv_k_tap<true>(p, k, c);
+        const int tapoff = conv_tap_step<true>(p, rs, dy, dx) + c;
         const unsigned kb = (unsigned)kt * (unsigned)p.Ncol * 64u;
 #pragma unroll
-        for (int i = 0; i < B_PASS; ++i) rb[i] = __builtin_amdgcn_raw_buffer_load_b128(rsB, (int)(bbase[i] + kb), 0, 0);
-    };
-    auto store_tile = [&](int buf, const u32x4 (&src)[A_PASS]) {
-        char *As = smem + buf * STAGE;
-        char *Bs = As + PA;
+        for (int i = 0; i < B_PASS; ++i)
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsB, (__attribute__((address_space(3))) void *)(Bs + i * ROWS * 64), 16,
+                                                     (int)(bbase[i] + kb), 0, 0, 0);
 #pragma unroll
-        for (int i = 0; i < A_PASS; ++i) *reinterpret_cast<u32x4 *>(As + st_off + i * ROWS * 64) = src[i];
-#pragma unroll
-        for (int i = 0; i < B_PASS; ++i) *reinterpret_cast<u32x4 *>(Bs + st_off + i * ROWS * 64) = rb[i];
+        for (int i = 0; i < A_PASS; ++i) {
+            // this thread's 16-byte chunk of A for row pass i (bit 31 set = out of range: zeros)
+            int off;
+            const int v = (int)kv & conv_tap_test<STRIDED>(p, ay[i], ax[i], abase[i], dy, dx, tapoff, c, off);
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsA, (__attribute__((address_space(3))) void *)(As + i * ROWS * 64), 16,
+                                                     (int)oob_unless((unsigned)off * 2u, v), 0, 0, 0);
+        }
     };
-
-    load_a(0, ra[0]);
-    load_b(0);
-    load_a(1, ra[1]);                        // past the end of K: out-of-range offsets, zeros
-    store_tile(0, ra[0]);
-    __syncthreads();
-    int kt = 0;
-    for (; kt + 2 <= KT - 1; kt += 2) {
-        {
-            load_b(kt + 1);
-            load_a(kt + 2, ra[0]);
-            __builtin_amdgcn_sched_barrier(0);
-            const char *As = smem;
-            mma_step<MR, NR>(As, As + PA, arow0, brow0, lane, acc);
-            store_tile(1, ra[1]);
-            __syncthreads();
-        }
-        {
-            load_b(kt + 2);
-            load_a(kt + 3, ra[1]);
-            __builtin_amdgcn_sched_barrier(0);
-            const char *As = smem + STAGE;
-            mma_step<MR, NR>(As, As + PA, arow0, brow0, lane, acc);
-            store_tile(0, ra[0]);
-            __syncthreads();
-        }
-    }
-    if (kt < KT - 1) {
-        load_b(kt + 1);
-        __builtin_amdgcn_sched_barrier(0);
-        const char *As = smem;
+    constexpr int NLD = A_PASS + B_PASS;              // LDS-DMA instructions per thread per K-step
+    constexpr int AHEAD = NST - 1;                    // K-steps in flight beyond the one being multiplied
+    // wait until the loads of step `kt + 1` have landed: those of the later steps already issued stay in flight
+    auto wait_next = [&](int kt) {
+        const int later = min(KT - 1, kt + AHEAD) - (kt + 1);       // steps issued beyond kt + 1
+        if (later >= 2) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * NLD) : "memory");
+        else if (later == 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NLD) : "memory");
+        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    };
+#pragma unroll
+    for (int i = 0; i < AHEAD; ++i)
+        if (i < KT) issue(i, i);
+    wait_next(-1);
+    __builtin_amdgcn_s_barrier();
+    int st = 0, kt = 0;                               // st: stage of K-step kt
+    // steady state as ONE basic block (unconditional issue, constant wait count) so that the scheduler may place the LDS-DMA
+    // pieces among the MFMAs; the last AHEAD steps, which issue nothing, follow.  (Tried as one function with conv_h2d_kernel's
+    // ring, conv_rows.h: the loops came out an instruction apart from these in most instances, so each kernel keeps its own.)
+    for (; kt + AHEAD < KT; ++kt) {
+        const int stn = st + AHEAD >= NST ? st + AHEAD - NST : st + AHEAD;
+        const char *As = smem + st * STAGE;
         mma_step<MR, NR>(As, As + PA, arow0, brow0, lane, acc);
-        store_tile(1, ra[1]);
-        __syncthreads();
-        ++kt;
+        issue(kt + AHEAD, stn);       // in program order BEHIND the fragment reads (LDS write after LDS reads)
+        // both halves' fragments first, then one LDS-DMA piece behind each of the first MFMAs: a piece's issue (tens of
+        // cycles) runs under the matrix pipe's work instead of ahead of it
+        __builtin_amdgcn_sched_group_barrier(0x100, 2 * (MR + NR), 0);
+#pragma unroll
+        for (int i = 0; i < NLD; ++i) {
+            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+            __builtin_amdgcn_sched_group_barrier(0x010, 1, 0);
+        }
+        __builtin_amdgcn_sched_group_barrier(0x008, 2 * MR * NR - NLD, 0);
+        // the MFMAs may sink below the barrier (registers only); the fragment reads may not: the next step's pieces overwrite
+        // this stage
+        asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"((AHEAD - 1) * NLD) : "memory");
+        __builtin_amdgcn_s_barrier();
+        st = st == NST - 1 ? 0 : st + 1;
     }
-    {
-        const char *As = smem + (kt & 1) * STAGE;
+    for (; kt < KT; ++kt) {
+        const char *As = smem + st * STAGE;
         mma_step<MR, NR>(As, As + PA, arow0, brow0, lane, acc);
-    }
+        wait_next(kt);
+        __builtin_amdgcn_s_barrier();
+        st = st == NST - 1 ? 0 : st + 1;
     }
 
     // epilogue.  Transposed accumulators: lane = pixel (lane & 31) of each row tile, registers 4g..4g+3 = output channels
     // 8g + 4(lane>>5) .. +3 of each column tile.
     const int l31 = lane & 31, kh = lane >> 5;
-    const bool full = p.rh == p.Ho && p.rw == p.Wo && p.rband <= 0;
     const bool want_stats = (!DGRAD || EP >= 2) && p.stats != nullptr;
     long lin[MR];
     bool rowok[MR];
+    const bool full = p.rh == p.Ho && p.rw == p.Wo && p.rband <= 0;
 #pragma unroll
     for (int mr = 0; mr < MR; ++mr) {
         const int row = m0 + arow0 + mr * 32 + l31;
@@ -642,7 +488,8 @@ __global__ void __launch_bounds__(64 * WM * WN, (WM * WN == 4 && NST == 3) ? 2 :
         }
         }
         if (want_stats) {                                 // block-uniform
-            // column sums over the 32 pixels (lanes) of this half-wavefront: a reduce-scatter butterfly (igemm_conv.hip)
+            // column sums over the 32 pixels (lanes) of this half-wavefront: a reduce-scatter butterfly (igemm_conv.hip
+            // conv_epilogue_tr has the same block and says why it is not one function)
             const bool b4 = lane & 16, b3 = lane & 8, b2 = lane & 4, b1 = lane & 2;
             float s8[8], q8[8], s4[4], q4[4], s2[2], q2[2];
 #pragma unroll
@@ -773,10 +620,10 @@ __global__ void __launch_bounds__(256, 2) wgrad_bf16_kernel(WgradParams p) {
             const bool v = acta && mk < klen;
             unsigned bo;
             if (REGION) {
-                bo = v ? (unsigned)(((wa[j].pn * p.Ho + wa[j].py) * p.Wo + wa[j].px) * p.dy_pitch + cha) * 2u : OOB;
+                bo = v ? (unsigned)(((wa[j].pn * p.Ho + wa[j].py) * p.Wo + wa[j].px) * p.dy_pitch + cha) * 2u : CONV_OOB;
                 advance(wa[j]);
             } else {
-                bo = v ? (unsigned)(mk * p.dy_pitch + cha) * 2u : OOB;
+                bo = v ? (unsigned)(mk * p.dy_pitch + cha) * 2u : CONV_OOB;
             }
             ra[j] = __builtin_amdgcn_raw_buffer_load_b128(rsA, (int)bo, 0, 0);
         }
@@ -786,7 +633,7 @@ __global__ void __launch_bounds__(256, 2) wgrad_bf16_kernel(WgradParams p) {
             const int sy = wb[j].py * p.stride - p.pad + col.r * p.dil;
             const int sx = wb[j].px * p.stride - p.pad + col.s * p.dil;
             const bool v = col.act && mk < klen && (unsigned)sy < (unsigned)p.H && (unsigned)sx < (unsigned)p.W;
-            const unsigned bo = v ? (unsigned)(((wb[j].pn * p.H + sy) * p.W + sx) * p.x_pitch + col.ch) * 2u : OOB;
+            const unsigned bo = v ? (unsigned)(((wb[j].pn * p.H + sy) * p.W + sx) * p.x_pitch + col.ch) * 2u : CONV_OOB;
             rb[j] = __builtin_amdgcn_raw_buffer_load_b128(rsB, (int)bo, 0, 0);
             advance(wb[j]);
         }
@@ -932,17 +779,8 @@ inline int conv_bn_of(int Ncol) { return Ncol <= 64 ? 64 : (Ncol <= 128 ? 128 : 
 template <bool OBF>
 int launch_conv(ConvParams &p, bool dgrad, hipStream_t st, int ep = 0) {
     p.s_magic = magic_of(p.S);
-    {
-        const int taps = p.K / p.Cs, kch = rcf_kchunk(korder_chunked(p.flags), taps, p.Cs, RCF_KCHUNK_BF16);
-        p.kch = kch ? kch : p.Cs;
-        p.rsch = taps * p.kch;
-        p.kch_magic = magic_of(p.kch);
-        p.rsch_magic = magic_of(p.rsch);
-    }
-    if ((long)(p.K + BKT) * p.rsch >= (1L << 32)) return RCF_EINVAL;
-    // 32-bit descriptor offsets: the images one row tile can touch must lie within 2 GiB of the first one
-    const long per_tile_imgs = 256 / (long)p.rr + 2;
-    if (per_tile_imgs * p.a_img_stride * 2 >= (1L << 31)) return RCF_EINVAL;
+    fill_korder(p, p.flags, p.K / p.Cs, p.Cs, RCF_KCHUNK_BF16);
+    if (!conv_offsets_fit(p.K + BKT, p.rsch, p.rr, p.a_img_stride, 2)) return RCF_EINVAL;
     const long bbytes = (long)rcf_cdiv(p.K, BKT) * p.Ncol * 64;
     if (bbytes >= (1L << 31)) return RCF_EINVAL;
     p.b_bytes = (int)bbytes;
@@ -960,19 +798,7 @@ int launch_conv(ConvParams &p, bool dgrad, hipStream_t st, int ep = 0) {
 // the GEMM view of a forward (x -> y) or data-gradient (dy -> dx) launch, rows restricted to `region`: everything but the operands
 // and the epilogue.  Returns 0 / RCF_EINVAL.
 int conv_geometry(ConvParams &p, const rcf_conv_shape *s, const rcf_conv_region *region, bool dgrad) {
-    p.flags = s->flags;
-    p.S = s->S;
-    if (dgrad) {
-        p.Ncol = s->Cin; p.K = s->R * s->S * s->Cout;
-        p.Ho = s->H; p.Wo = s->W; p.Hs = s->Ho; p.Ws = s->Wo; p.Cs = s->Cout;
-        p.up = 1; p.off = s->pad; p.step = -s->dil; p.div = s->stride;
-        p.a_pitch = s->y_pitch; p.a_img_stride = (long)s->Ho * s->Wo * s->y_pitch; p.y_pitch = s->x_pitch;
-    } else {
-        p.Ncol = s->Cout; p.K = s->R * s->S * s->Cin;
-        p.Ho = s->Ho; p.Wo = s->Wo; p.Hs = s->H; p.Ws = s->W; p.Cs = s->Cin;
-        p.up = s->stride; p.off = -s->pad; p.step = s->dil; p.div = 1;
-        p.a_pitch = s->x_pitch; p.a_img_stride = (long)s->H * s->W * s->x_pitch; p.y_pitch = s->y_pitch;
-    }
+    fill_gemm_view(p, s, dgrad);
     return set_region(p, region, s->N, p.Ho, p.Wo);
 }
 

@@ -101,13 +101,7 @@ struct IgemmParams {
     int add_pitch;
 };
 
-// pixel `pix` of a region in the row-major order (region_order.h): the weight gradients (the order of their sums over pixels) and
-// the kernels without tap lists (conv_h2d_kernel, conv_h2p_kernel)
-__device__ __forceinline__ void region_yx(int pix, int ry0, int rx0, int rh, int rw, int t, int &y, int &x) {
-    rcf_region_yx(pix, ry0, rx0, rh, rw, t, RCF_REGION_ROWMAJOR, y, x);
-}
-
-__device__ __forceinline__ int fast_div(int k, unsigned magic) { return magic ? (int)__umulhi((unsigned)k, magic) : k; }
+#include "conv_rows.h"                        // what the forward / data-gradient kernels of this file and of igemm_bf16.hip share
 
 // K-major LDS tiles (X[k][ld]): operand fetch is one conflict-free ds_read_b32 per K=2 MFMA.
 template <int MR, int NR, int BKT>
@@ -518,8 +512,7 @@ __device__ __forceinline__ void mma_x3(const char *__restrict__ As, const char *
                                    : __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[mr][QA[t]], b[nr][QB[t]], acc[mr][nr], 0, 0, 0);
 }
 
-constexpr unsigned X3_OOB = 0x80000000u;      // byte offset beyond every descriptor's num_records: loads return 0
-#include "wgrad_cols.h"                       // oob_unless, lds_tr16, and what the tap-column weight gradients share
+#include "wgrad_cols.h"                       // lds_tr16, and what the tap-column weight gradients share
 
 // The epilogue of the transposed-accumulator conv kernels (igemm_conv_x3_kernel, conv_h2d_kernel): a lane owns pixel lane&31 of
 // each row tile and, per register quad, output channels 8g + 4(lane>>5) .. +3 of each column tile -- 16-byte stores, the region walk
@@ -533,9 +526,7 @@ __device__ __forceinline__ void conv_epilogue_tr(const IgemmParams &p, f32x16 (&
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wm = wave / WN, wn = wave - wm * WN;
     const int arow0 = wm * 32 * MR, brow0 = wn * 32 * NR;
-    const int HoWo = p.rr;
     const int l31 = lane & 31, kh = lane >> 5;
-    const bool full = p.rh == p.Ho && p.rw == p.Wo && p.rband <= 0;   // rows map linearly onto the output tensor
     const bool want_stats = !DGRAD && p.stats != nullptr;
     // BST: the batch-norm backward's two sums (lean path only: the launch checks) -- its own instantiation: the sums' registers
     // (32 accumulators beside the tile's 128) would cost every other data gradient occupancy or spills
@@ -546,6 +537,8 @@ __device__ __forceinline__ void conv_epilogue_tr(const IgemmParams &p, f32x16 (&
     // channels 8g + 4(lane>>5) .. +3 of each column tile: 16-byte stores, the region walk once per pixel
     long lin[MR];
     bool rowok[MR];
+    const int HoWo = p.rr;
+    const bool full = p.rh == p.Ho && p.rw == p.Wo && p.rband <= 0;   // rows map linearly onto the output tensor
 #pragma unroll
     for (int mr = 0; mr < MR; ++mr) {
         const int row = m0 + arow0 + mr * 32 + l31;
@@ -697,7 +690,9 @@ __device__ __forceinline__ void conv_epilogue_tr(const IgemmParams &p, f32x16 (&
         if (want_stats || want_bstats) {                  // block-uniform
             // column sums over the 32 pixels (lanes) of this half-wavefront: a reduce-scatter butterfly -- at every
             // step a lane keeps the half of its registers its lane bit selects and adds the partner's copy of them
-            // (16 + 8 + 4 + 2 + 1 values move instead of 5 x 16); bit 0 of the lane ends up redundant.
+            // (16 + 8 + 4 + 2 + 1 values move instead of 5 x 16); bit 0 of the lane ends up redundant.  (conv_bf16_kernel has
+            // the same block: as one function of conv_rows.h it cost the 64 x 64 bf16-triple tap-list forward 12 VGPRs and a
+            // wave per SIMD, so both stay inline.)
             const bool b4 = lane & 16, b3 = lane & 8, b2 = lane & 4, b1 = lane & 2;
             float s8[8], q8[8], s4[4], q4[4], s2[2], q2[2];
 #pragma unroll
@@ -799,7 +794,7 @@ __global__ void __launch_bounds__(64 * WM * WN, (MR * NR >= 8 && WM * WN == 4) ?
     const int HoWo = p.rr;                                    // rows per image (the region's pixels)
     const int n_first = m0 / HoWo;                            // first image this tile touches (block-uniform)
     const __amdgpu_buffer_rsrc_t rsA = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<float *>(p.A + (long)n_first * p.a_img_stride), 0, (int)X3_OOB, 0x00020000);
+        const_cast<float *>(p.A + (long)n_first * p.a_img_stride), 0, (int)CONV_OOB, 0x00020000);
     const __amdgpu_buffer_rsrc_t rsB = __builtin_amdgcn_make_buffer_rsrc(
         (NP == 2 && PRE) ? const_cast<void *>(p.b_pairs) : (void *)const_cast<float *>(p.Bw), 0, p.b_bytes, 0x00020000);
 
@@ -817,17 +812,8 @@ __global__ void __launch_bounds__(64 * WM * WN, (MR * NR >= 8 && WM * WN == 4) ?
             abase[i] = ok ? (m - n_first * HoWo) * p.a_pitch : 0;
             ay[i] = ok ? 0 : -(1 << 28);
             ax[i] = ok ? 0 : -(1 << 28);
-        } else if (m < p.M) {
-            const int n = m / HoWo;
-            int y, x;
-            rcf_region_yx(m - n * HoWo, p.ry0, p.rx0, p.rh, p.rw, p.rband, p.rorder, y, x);
-            ay[i] = y * p.up + p.off;
-            ax[i] = x * p.up + p.off;
-            abase[i] = (n - n_first) * (int)p.a_img_stride + (STRIDED ? 0 : (ay[i] * p.Ws + ax[i]) * p.a_pitch);
         } else {
-            abase[i] = 0;
-            ay[i] = -(1 << 28);
-            ax[i] = -(1 << 28);
+            conv_row_origin<STRIDED>(p, m, p.M, n_first, p.rorder, ay[i], ax[i], abase[i]);
         }
     }
     // fp16 pairs with the weights split beforehand: same addresses, 16 bytes = (h0..h3, m0..m3) of four k
@@ -836,7 +822,7 @@ __global__ void __launch_bounds__(64 * WM * WN, (MR * NR >= 8 && WM * WN == 4) ?
 #pragma unroll
     for (int i = 0; i < B_PASS; ++i) {
         const int j = n0 + arow + ROWS * i;
-        bbase[i] = j < p.Ncol ? (unsigned)j * (pre ? 64u : (unsigned)p.ldb * 4u) : X3_OOB;
+        bbase[i] = j < p.Ncol ? (unsigned)j * (pre ? 64u : (unsigned)p.ldb * 4u) : CONV_OOB;
     }
     // A (activations) comes from HBM: its loads run TWO K-steps ahead (two register sets, ping-pong by the parity
     // of the step); B (weights, L2 resident) one step ahead.
@@ -848,34 +834,19 @@ __global__ void __launch_bounds__(64 * WM * WN, (MR * NR >= 8 && WM * WN == 4) ?
         constexpr bool BAND = decltype(BAND_)::value;
         const int k = kt * BKT + kq * 4;
         const bool kv = k < p.K;
-        // position k of the K loop = (channel chunk q, tap rs, channel inside the chunk); natural order: ONE chunk of Cs
-        const int q = fast_div(k, p.rsch_magic);
-        const int rem = k - q * p.rsch;
-        const int rs = fast_div(rem, p.kch_magic);
-        const int c = q * p.kch + (rem - rs * p.kch);
-        const int r = fast_div(rs, p.s_magic);
-        const int s = rs - r * p.S;
-        const int dy = r * p.step, dx = s * p.step;
-        const int tapoff = (dy * p.Ws + dx) * p.a_pitch + c;
+        int c, dy, dx;
+        const int rs = conv_k_tap<false>(p, k, c);
+        const int tapoff = conv_tap_step<false>(p, rs, dy, dx) + c;
 #pragma unroll
         for (int i = 0; i < A_PASS; ++i) {
-            int ty = ay[i] + dy, tx = ax[i] + dx;
-            int v, off;                      // v: 0 / 1, combined with bitwise ops (no short-circuit control flow)
-            if (STRIDED) {
-                v = (int)kv & (int)(ty >= 0) & (int)(tx >= 0) & (int)(ty % p.div == 0) & (int)(tx % p.div == 0);
-                ty /= p.div;
-                tx /= p.div;
-                v &= (int)(ty < p.Hs) & (int)(tx < p.Ws);
-                off = abase[i] + (ty * p.Ws + tx) * p.a_pitch + c;
-            } else {
-                v = (int)kv & (int)((unsigned)ty < (unsigned)p.Hs) & (int)((unsigned)tx < (unsigned)p.Ws);
-                if constexpr (BAND)
-                    v &= (int)(ty < band_lo) | (int)(ty >= p.Hs - band_lo) | (int)(tx < band_lo) | (int)(tx >= p.Ws - band_lo);
-                off = abase[i] + tapoff;
+            int off;
+            int v = (int)kv & conv_tap_test<STRIDED>(p, ay[i], ax[i], abase[i], dy, dx, tapoff, c, off);
+            if constexpr (BAND) {
+                const int ty = ay[i] + dy, tx = ax[i] + dx;
+                v &= (int)(ty < band_lo) | (int)(ty >= p.Hs - band_lo) | (int)(tx < band_lo) | (int)(tx >= p.Ws - band_lo);
             }
             // invalid -> offset with bit 31 set (beyond num_records): the load returns zeros without touching memory
-            const unsigned bo = (((unsigned)off * 4u) & ~X3_OOB) | ((unsigned)(v - 1) & X3_OOB);
-            dst[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsA, (int)bo, 0, 0));
+            dst[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsA, (int)oob_unless((unsigned)off * 4u, v), 0, 0));
         }
     };
     auto load_b = [&](int kt) {
@@ -886,12 +857,11 @@ __global__ void __launch_bounds__(64 * WM * WN, (MR * NR >= 8 && WM * WN == 4) ?
         if constexpr (pre) {
             k4 = (unsigned)kt * (unsigned)p.Ncol * 64u + (unsigned)kq * 16u;
         } else {
-            const int q = fast_div(k, p.rsch_magic);
-            const int rem = k - q * p.rsch;
-            const int rs = fast_div(rem, p.kch_magic);
-            k4 = (unsigned)(rs * p.Cs + q * p.kch + (rem - rs * p.kch)) * 4u;
+            int c;
+            const int rs = conv_k_tap<false>(p, k, c);
+            k4 = (unsigned)(rs * p.Cs + c) * 4u;
         }
-        const unsigned koob = (unsigned)((int)(k < p.K) - 1) & X3_OOB;
+        const unsigned koob = (unsigned)((int)(k < p.K) - 1) & CONV_OOB;
 #pragma unroll
         for (int i = 0; i < B_PASS; ++i)
             rb[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsB, (int)((bbase[i] + k4) | koob), 0, 0));
@@ -968,9 +938,8 @@ __global__ void __launch_bounds__(64 * WM * WN, (MR * NR >= 8 && WM * WN == 4) ?
             // first listed K-step after kt (KT: none left -- a step past the end of K loads zeros, like the plain loop's look-ahead)
             auto next = [&](int kt) {
                 while (++kt < KT) {
-                    const int k = kt * BKT;
-                    const int rem = k - fast_div(k, p.rsch_magic) * p.rsch;
-                    if ((taps >> fast_div(rem, p.kch_magic)) & 1u) return kt;
+                    int c;
+                    if ((taps >> conv_k_tap<false>(p, kt * BKT, c)) & 1u) return kt;
                 }
                 return KT;
             };
@@ -1440,9 +1409,9 @@ __global__ void __launch_bounds__(256) igemm_wgrad_x3_kernel(WgradParams p) {
     const int HoWo = p.rr;                        // contributing pixels per image
     const int n_first = (int)(kbeg / HoWo);
     const __amdgpu_buffer_rsrc_t rsA = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<float *>(p.DY + (long)n_first * p.Ho * p.Wo * p.dy_pitch), 0, (int)X3_OOB, 0x00020000);
+        const_cast<float *>(p.DY + (long)n_first * p.Ho * p.Wo * p.dy_pitch), 0, (int)CONV_OOB, 0x00020000);
     const __amdgpu_buffer_rsrc_t rsB = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<float *>(p.X + (long)n_first * p.H * p.W * p.x_pitch), 0, (int)X3_OOB, 0x00020000);
+        const_cast<float *>(p.X + (long)n_first * p.H * p.W * p.x_pitch), 0, (int)CONV_OOB, 0x00020000);
 
     const int ch = (isB ? j0 : i0) + 4 * q;
     const bool active = isB ? (q < BN / 4 && ch < p.Cin) : (q < BM / 4 && ch < p.Cout);
@@ -1469,13 +1438,13 @@ __global__ void __launch_bounds__(256) igemm_wgrad_x3_kernel(WgradParams p) {
             const int oy = py[i], ox = px_[i];                              // output pixel in the image
             if (!isB) {
                 const bool v = active && mk < klen;
-                const unsigned bo = v ? (unsigned)(((pn[i] * p.Ho + oy) * p.Wo + ox) * p.dy_pitch + ch) * 4u : X3_OOB;
+                const unsigned bo = v ? (unsigned)(((pn[i] * p.Ho + oy) * p.Wo + ox) * p.dy_pitch + ch) * 4u : CONV_OOB;
                 rr[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsA, (int)bo, 0, 0));
             } else {
                 const int sy = oy * p.stride - p.pad + r * p.dil;
                 const int sx = ox * p.stride - p.pad + s * p.dil;
                 const bool v = active && mk < klen && (unsigned)sy < (unsigned)p.H && (unsigned)sx < (unsigned)p.W;
-                const unsigned bo = v ? (unsigned)(((pn[i] * p.H + sy) * p.W + sx) * p.x_pitch + ch) * 4u : X3_OOB;
+                const unsigned bo = v ? (unsigned)(((pn[i] * p.H + sy) * p.W + sx) * p.x_pitch + ch) * 4u : CONV_OOB;
                 rr[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsB, (int)bo, 0, 0));
             }
             if (incr) {                          // rw >= BK: at most one row wrap per K-step
@@ -1618,9 +1587,9 @@ __global__ void __launch_bounds__(256, 2) igemm_wgrad_x3_wide_kernel(WgradParams
     const int HoWo = p.Ho * p.Wo;
     const int n_first = (int)(kbeg / HoWo);
     const __amdgpu_buffer_rsrc_t rsA = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<float *>(p.DY + kbeg * p.dy_pitch), 0, (int)X3_OOB, 0x00020000);
+        const_cast<float *>(p.DY + kbeg * p.dy_pitch), 0, (int)CONV_OOB, 0x00020000);
     const __amdgpu_buffer_rsrc_t rsB = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<float *>(p.X + (long)n_first * p.H * p.W * p.x_pitch), 0, (int)X3_OOB, 0x00020000);
+        const_cast<float *>(p.X + (long)n_first * p.H * p.W * p.x_pitch), 0, (int)CONV_OOB, 0x00020000);
 
     const int cha = i0 + 4 * qa, chb = j0 + 4 * q;
     const bool acta = cha < p.Cout, actb = chb < p.Cin;
@@ -1644,7 +1613,7 @@ __global__ void __launch_bounds__(256, 2) igemm_wgrad_x3_wide_kernel(WgradParams
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
             const int mk = kt * BK + 2 * g2 + i;
-            const unsigned bo = (acta && mk < klen) ? (unsigned)(mk * p.dy_pitch + cha) * 4u : X3_OOB;
+            const unsigned bo = (acta && mk < klen) ? (unsigned)(mk * p.dy_pitch + cha) * 4u : CONV_OOB;
             ra[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsA, (int)bo, 0, 0));
         }
 #pragma unroll
@@ -1653,7 +1622,7 @@ __global__ void __launch_bounds__(256, 2) igemm_wgrad_x3_wide_kernel(WgradParams
             const int sy = py[i] * p.stride - p.pad + r * p.dil;
             const int sx = px_[i] * p.stride - p.pad + s * p.dil;
             const bool v = actb && mk < klen && (unsigned)sy < (unsigned)p.H && (unsigned)sx < (unsigned)p.W;
-            const unsigned bo = v ? (unsigned)(((pn[i] * p.H + sy) * p.W + sx) * p.x_pitch + chb) * 4u : X3_OOB;
+            const unsigned bo = v ? (unsigned)(((pn[i] * p.H + sy) * p.W + sx) * p.x_pitch + chb) * 4u : CONV_OOB;
             rb[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsB, (int)bo, 0, 0));
             if (incr) {
                 px_[i] += BK;
@@ -2096,23 +2065,19 @@ int plan_conv(const IgemmParams &p, int batches, bool presplit, ConvPlan &pl) {
         plan_tiles(pl, p, 1);
         return 0;
     }
-    const int taps = p.K / p.Cs, kch = rcf_kchunk(korder_chunked(p.flags), taps, p.Cs, RCF_KCHUNK_F32);
-    pl.kch = kch ? kch : p.Cs;
-    pl.rsch = taps * pl.kch;
-    pl.kch_magic = magic_of(pl.kch);
-    pl.rsch_magic = magic_of(pl.rsch);
-    if ((long)(p.K + 16) * pl.rsch >= (1L << 32)) return RCF_EINVAL;
+    const int taps = p.K / p.Cs;
+    fill_korder(pl, p.flags, taps, p.Cs, RCF_KCHUNK_F32);
+    // 32-bit descriptor offsets (every kernel from here on): the K walk, the images of one row tile -- and, below, the weights
+    if (!conv_offsets_fit(p.K + 16, pl.rsch, p.rr, p.a_img_stride, 4)) return RCF_EINVAL;
     pl.np = (p.amax_a && p.amax_b) ? 2 : 3;
     pl.pre = pl.np == 2 && presplit;
     pl.rorder = RCF_REGION_ROWMAJOR;             // conv_h2d_kernel / conv_h2p_kernel: no tap lists, the order they always had
-    // 32-bit descriptor offsets: the images one row tile can touch must lie within 2 GiB of the first one, and so must the weights
-    const bool far = (256 / (long)p.rr + 2) * p.a_img_stride * 4 >= (1L << 31);
     const long dma_bytes = (long)(p.K / 16) * p.Ncol * 64;            // the plane-separated K-step blocks (b_pairs2)
     if (p.a_split) {
         // conv_h2d_kernel (igemm_h2d.inc): the activation operand arrives as fp16 pair planes -- the only kernel that reads them
         if (p.src_band > 0 || !p.b_pairs2 || !p.amax_a || !p.amax_b || batches != 1 || p.batch1 > 0) return RCF_EINVAL;
         if (p.K % 16 || p.Cs % 16 || p.a_pitch != p.Cs || p.Ncol % 4) return RCF_EINVAL;
-        if (dma_bytes >= (1L << 31) || far) return RCF_EINVAL;
+        if (dma_bytes >= (1L << 31)) return RCF_EINVAL;
         pl.kernel = RCF_KERNEL_H2D;
         pl.b_bytes = (int)dma_bytes;
         pl.mr = 2; pl.nr = p.Ncol > 128 ? 4 : (p.Ncol > 64 ? 2 : 1);
@@ -2121,7 +2086,7 @@ int plan_conv(const IgemmParams &p, int batches, bool presplit, ConvPlan &pl) {
         return 0;
     }
     if (h2p_eligible(p, batches)) {
-        if (dma_bytes >= (1L << 31) || far) return RCF_EINVAL;
+        if (dma_bytes >= (1L << 31)) return RCF_EINVAL;
         pl.kernel = RCF_KERNEL_H2P;
         pl.b_bytes = (int)dma_bytes;
         pl.nr = 4;
@@ -2133,7 +2098,7 @@ int plan_conv(const IgemmParams &p, int batches, bool presplit, ConvPlan &pl) {
         return 0;
     }
     pl.kernel = RCF_KERNEL_TILE;
-    if (far || (long)p.Ncol * p.ldb * 4 >= (1L << 31)) return RCF_EINVAL;
+    if ((long)p.Ncol * p.ldb * 4 >= (1L << 31)) return RCF_EINVAL;
     pl.b_bytes = (int)((long)p.Ncol * p.ldb * 4);
     const long pair_bytes = (long)rcf_cdiv(p.K, 16) * p.Ncol * 64;      // K-step-major pairs: K padded to whole steps
     if (pl.pre && pair_bytes >= (1L << 31)) return RCF_EINVAL;
@@ -2368,13 +2333,9 @@ namespace {
 int fwd_params(IgemmParams &p, const float *x, const float *w, const float *bias, float *y, const rcf_conv_shape *s,
                const rcf_conv_region *region, int act, float slope, int beta, double *stats) {
     if (!use_x3(s->flags) && (region || stats)) return RCF_EINVAL;     // sub-rectangles / fused statistics exist on the default kernels only
-    p.flags = s->flags;
+    fill_gemm_view(p, s, false);
     p.A = x; p.Bw = w; p.bias = bias; p.Y = y;
-    p.Ncol = s->Cout; p.K = s->R * s->S * s->Cin;
-    p.Ho = s->Ho; p.Wo = s->Wo; p.Hs = s->H; p.Ws = s->W; p.Cs = s->Cin; p.S = s->S;
     if (int e = set_region(p, region, s->N, s->Ho, s->Wo)) return e;
-    p.up = s->stride; p.off = -s->pad; p.step = s->dil; p.div = 1;
-    p.a_pitch = s->x_pitch; p.a_img_stride = (long)s->H * s->W * s->x_pitch; p.y_pitch = s->y_pitch;
     p.ldb = p.K; p.act = act; p.slope = slope; p.beta = beta;
     p.amax_a = s->amax_x; p.amax_b = s->amax_w; p.b_pairs = s->w_pairs;
     if (s->w_pairs2) {
@@ -2404,7 +2365,7 @@ int dgrad_params(IgemmParams &p, const float *dy, const float *w, float *dx, con
                  int dy_band, int beta, const DgradFused &f) {
     if (s->Cout % 4) return RCF_EINVAL;
     if (!use_x3(s->flags) && (region || f.bn)) return RCF_EINVAL;
-    p.flags = s->flags;
+    fill_gemm_view(p, s, true);
     if (dy_band > 0) {                           // the source frame lives in igemm_conv_x3_kernel's tap-list loop
         p.flags |= RCF_CONV_H2P_NEVER;
         p.src_band = dy_band;
@@ -2428,11 +2389,7 @@ int dgrad_params(IgemmParams &p, const float *dy, const float *w, float *dx, con
         p.bn_x = bn->x; p.bn_x_pitch = bn->x_pitch; p.bn_mask = bn->relu_mask; p.bn_mean = bn->mean; p.bn_invstd = bn->invstd;
     }
     p.A = dy; p.Bw = w; p.bias = nullptr; p.Y = dx;
-    p.Ncol = s->Cin; p.K = s->R * s->S * s->Cout;
-    p.Ho = s->H; p.Wo = s->W; p.Hs = s->Ho; p.Ws = s->Wo; p.Cs = s->Cout; p.S = s->S;
     if (int e = set_region(p, region, s->N, s->H, s->W)) return e;
-    p.up = 1; p.off = s->pad; p.step = -s->dil; p.div = s->stride;
-    p.a_pitch = s->y_pitch; p.a_img_stride = (long)s->Ho * s->Wo * s->y_pitch; p.y_pitch = s->x_pitch;
     p.ldb = s->R * s->S * s->Cin; p.act = 0; p.slope = 0.f; p.beta = beta;
     if (!use_x3(s->flags)) return 0;
     // the default kernels contract against k-contiguous weights wt[c][rs][co]: prepared once per weight update by the caller (with

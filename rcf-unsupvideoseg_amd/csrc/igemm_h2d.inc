@@ -19,10 +19,6 @@
 // 16-byte halves of a row are swapped on rows with bit 3 set (mma_x3's conflict-free fragment layout), which for the activation
 // operand is applied to the SOURCE address and for the weights is already in the memory image.
 
-__device__ __forceinline__ int h2d_div_nb(int k, unsigned magic) {      // k / d without a branch on the (uniform) d == 1 case
-    return (int)(__umulhi((unsigned)k, magic) + ((unsigned)k & (magic ? 0u : ~0u)));
-}
-
 template <int NR, bool STRIDED, bool DGRAD, bool BST = false>
 __global__ void __launch_bounds__(256, 2) conv_h2d_kernel(IgemmParams p) {
     constexpr int MR = 2, WM = 2, WN = 2;
@@ -43,7 +39,7 @@ __global__ void __launch_bounds__(256, 2) conv_h2d_kernel(IgemmParams p) {
     const int HoWo = p.rr;
     const int n_first = m0 / HoWo;
     const __amdgpu_buffer_rsrc_t rsA = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<float *>(p.A + (long)n_first * p.a_img_stride), 0, (int)X3_OOB, 0x00020000);
+        const_cast<float *>(p.A + (long)n_first * p.a_img_stride), 0, (int)CONV_OOB, 0x00020000);
     const __amdgpu_buffer_rsrc_t rsB = __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(p.b_pairs2), 0, p.b_bytes, 0x00020000);
 
     // ---- A: this thread serves tile row 32 wave + lane / 2 in both planes; its LDS position holds half (lane & 1), which on
@@ -52,21 +48,7 @@ __global__ void __launch_bounds__(256, 2) conv_h2d_kernel(IgemmParams p) {
     const int srch = (lane & 1) ^ ((arow >> 3) & 1);
     const int plane_b = 2 * p.a_pitch;                        // bytes from the h plane to the m plane of a pixel
     int abase, ay, ax;                                        // fp32-element offset of tap (0, 0) of the row (STRIDED: of the image)
-    {
-        const int m = m0 + arow;
-        if (m < p.M) {
-            const int n = m / HoWo;
-            int y, x;
-            region_yx(m - n * HoWo, p.ry0, p.rx0, p.rh, p.rw, p.rband, y, x);
-            ay = y * p.up + p.off;
-            ax = x * p.up + p.off;
-            abase = (n - n_first) * (int)p.a_img_stride + (STRIDED ? 0 : (ay * p.Ws + ax) * p.a_pitch);
-        } else {
-            abase = 0;
-            ay = -(1 << 28);
-            ax = -(1 << 28);
-        }
-    }
+    conv_row_origin<STRIDED>(p, m0 + arow, p.M, n_first, RCF_REGION_ROWMAJOR, ay, ax, abase);
     // ---- B: NR pieces of 32 weight rows per wave: planes {0, 1} x row blocks {wave, wave + 4, ..} (NR = 1: one piece,
     // plane wave / 2, row block wave % 2).  The memory image is the LDS image: a piece is 1 KB of consecutive bytes.
     unsigned bbase[NR];
@@ -76,34 +58,17 @@ __global__ void __launch_bounds__(256, 2) conv_h2d_kernel(IgemmParams p) {
         const int plane = NR >= 2 ? (i & 1) : (wave >> 1);
         const int rb = NR >= 2 ? wave + 4 * (i >> 1) : (wave & 1);
         const int j = n0 + 32 * rb + (lane >> 1);
-        bbase[i] = j < p.Ncol ? ((unsigned)plane * (unsigned)p.Ncol + (unsigned)j) * 32u + (unsigned)(lane & 1) * 16u : X3_OOB;
+        bbase[i] = j < p.Ncol ? ((unsigned)plane * (unsigned)p.Ncol + (unsigned)j) * 32u + (unsigned)(lane & 1) * 16u : CONV_OOB;
         bdst[i] = 2 * PA + plane * PB + rb * 1024;
     }
     const unsigned kstride = 2u * (unsigned)p.Ncol * 32u;      // bytes of one K-step of the weight operand (two planes)
 
     auto issue = [&](int kt, int stage) {
         char *st = smem + stage * STAGE;
-        const int k = kt * BKT + 8 * srch;
-        // position k of the K loop = (channel chunk q, tap rs, channel inside the chunk); natural order: ONE chunk of Cs
-        const int q = h2d_div_nb(k, p.rsch_magic);
-        const int rem = k - q * p.rsch;
-        const int rs = h2d_div_nb(rem, p.kch_magic);
-        const int c = q * p.kch + (rem - rs * p.kch);
-        const int r = h2d_div_nb(rs, p.s_magic);
-        const int s = rs - r * p.S;
-        const int dy = r * p.step, dx = s * p.step;
-        int ty = ay + dy, tx = ax + dx;
-        int v, off;
-        if (STRIDED) {
-            v = (int)(ty >= 0) & (int)(tx >= 0) & (int)(ty % p.div == 0) & (int)(tx % p.div == 0);
-            ty /= p.div;
-            tx /= p.div;
-            v &= (int)(ty < p.Hs) & (int)(tx < p.Ws);
-            off = abase + (ty * p.Ws + tx) * p.a_pitch;
-        } else {
-            v = (int)((unsigned)ty < (unsigned)p.Hs) & (int)((unsigned)tx < (unsigned)p.Ws);
-            off = abase + (dy * p.Ws + dx) * p.a_pitch;
-        }
+        int c, dy, dx, off;                      // (the launch checks K % 16 == 0: no step runs past the end of K)
+        const int rs = conv_k_tap<true>(p, kt * BKT + 8 * srch, c);
+        const int tapoff = conv_tap_step<true>(p, rs, dy, dx);
+        const int v = conv_tap_test<STRIDED>(p, ay, ax, abase, dy, dx, tapoff, 0, off);
         const unsigned b0 = (unsigned)off * 4u + (unsigned)c * 2u;
 #pragma unroll
         for (int i = 0; i < NR; ++i)
@@ -125,6 +90,8 @@ __global__ void __launch_bounds__(256, 2) conv_h2d_kernel(IgemmParams p) {
     const int arow0 = wm * 32 * MR, brow0 = wn * 32 * NR;
     const int KT = p.K / BKT;                                 // the launch checks K % 16 == 0
 
+    // (This ring and conv_bf16_kernel's were tried as one function of (KT, issue, mma) in conv_rows.h: the steady-state loops came
+    // out an instruction apart from the ones below in most instances of both kernels, so each kernel keeps its own.)
     // wait until the pieces of step kt + 1 have landed: those of later steps already issued stay in flight
     auto wait_next = [&](int kt) {
         const int later = min(KT - 1, kt + AHEAD) - (kt + 1);

@@ -1,5 +1,5 @@
 // Persistent fp16-pair implicit-GEMM kernel ("h2p") for the wide, deep convolutions of the training step -- included by
-// igemm_conv.hip inside its anonymous namespace (IgemmParams, region_yx, fast_div, split2h, h2_exponent, pow2f, X3_OOB).
+// igemm_conv.hip inside its anonymous namespace (IgemmParams, region_yx, fast_div, split2h, h2_exponent, pow2f, CONV_OOB).
 //
 // Why a second kernel.  igemm_conv_x3_kernel (128 x 256 tile, 4 waves, 2 workgroups per CU) keeps the matrix pipe 54-60 %
 // busy: two unsynchronised waves share each SIMD and take turns, every wave's K-step is "read fragments, 24 MFMAs, split,
@@ -61,7 +61,7 @@ __device__ __forceinline__ void h2p_tile(const IgemmParams &p, char *__restrict_
     const int HoWo = p.rr;
     const int n_first = row0 / HoWo;                       // first image this tile touches (block-uniform)
     const __amdgpu_buffer_rsrc_t rsA = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<float *>(p.A + (long)n_first * p.a_img_stride), 0, (int)X3_OOB, 0x00020000);
+        const_cast<float *>(p.A + (long)n_first * p.a_img_stride), 0, (int)CONV_OOB, 0x00020000);
     const __amdgpu_buffer_rsrc_t rsB =
         __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(p.b_pairs2), 0, p.b_bytes, 0x00020000);
 
@@ -72,18 +72,7 @@ __device__ __forceinline__ void h2p_tile(const IgemmParams &p, char *__restrict_
         const int r = arow + 64 * i;
         const int m = row0 + r;
         st_off[i] = r * 32 + ((((kq >> 1) ^ ((r >> 3) & 1))) << 4) + (kq & 1) * 8;
-        if (m < row_end) {
-            const int n = m / HoWo;
-            int y, x;
-            region_yx(m - n * HoWo, p.ry0, p.rx0, p.rh, p.rw, p.rband, y, x);
-            ay[i] = y * p.up + p.off;
-            ax[i] = x * p.up + p.off;
-            abase[i] = (n - n_first) * (int)p.a_img_stride + (ay[i] * p.Ws + ax[i]) * p.a_pitch;
-        } else {
-            abase[i] = 0;
-            ay[i] = -(1 << 28);
-            ax[i] = -(1 << 28);
-        }
+        conv_row_origin<false>(p, m, row_end, n_first, RCF_REGION_ROWMAJOR, ay[i], ax[i], abase[i]);
     }
     // K walk of the A loads: K-steps are loaded in order (0, 1, 2, ...), Cs % 16 == 0, so a step lies inside one filter tap and
     // (tap, first channel) advance by scalar arithmetic -- no division, no per-thread work
@@ -97,10 +86,9 @@ __device__ __forceinline__ void h2p_tile(const IgemmParams &p, char *__restrict_
         const int tapoff = (dy * p.Ws + dx) * p.a_pitch + lcb + lc + kq * 4;
 #pragma unroll
         for (int i = 0; i < A_PASS; ++i) {
-            const int ty = ay[i] + dy, tx = ax[i] + dx;
-            const int v = kv & (int)((unsigned)ty < (unsigned)p.Hs) & (int)((unsigned)tx < (unsigned)p.Ws);
-            const unsigned bo = (((unsigned)(abase[i] + tapoff) * 4u) & ~X3_OOB) | ((unsigned)(v - 1) & X3_OOB);
-            dst[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsA, (int)bo, 0, 0));
+            int off;
+            const int v = kv & conv_tap_test<false>(p, ay[i], ax[i], abase[i], dy, dx, tapoff, 0, off);
+            dst[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsA, (int)oob_unless((unsigned)off * 4u, v), 0, 0));
         }
         lk += 16;
         lc += 16;

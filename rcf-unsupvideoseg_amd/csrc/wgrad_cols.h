@@ -11,9 +11,8 @@
 // the tile store, the three-stage K-loop of the two DMA kernels, and those two kernels' whole body over an operand type
 // (wgrad_dma_body: their __global__ wrappers hold the LDS array and the launch bounds).
 // Included by igemm_conv.hip and igemm_bf16.hip, once each, inside their unnamed namespace (so that the kernels stay file-local),
-// after rcf_common.h (f32x16, rcf_wgrad_item, rcf_wgrad_tile_ij, h2_exponent, pow2f), their u32x2 / u32x4 typedefs and their
-// region_yx (the two files walk a frame in their own ways; each kernel keeps its file's).  The asserts below turn a missing one
-// into one message.
+// after rcf_common.h (f32x16, rcf_wgrad_item, rcf_wgrad_tile_ij, h2_exponent, pow2f) and their u32x2 / u32x4 typedefs.  The
+// asserts below turn a missing one into one message.
 #pragma once
 static_assert(sizeof(u32x2) == 8 && sizeof(u32x4) == 16 && sizeof(f32x16) == 64,
               "wgrad_cols.h: include after rcf_common.h and the u32x2 / u32x4 typedefs");
@@ -40,10 +39,7 @@ struct WgradParamsT {
     int Ktot;          // R*S*Cin: the GEMM columns of the tap-column kernels
 };
 
-constexpr unsigned WGRAD_OOB = 0x80000000u;      // byte offset beyond every descriptor's num_records: loads return 0
-// byte offset `off` if ok == 1, an out-of-range offset (the load returns zeros) if ok == 0 -- arithmetic, so that a K-step's
-// loads stay in one basic block (a select on a load's address tends to become a branch)
-__device__ __forceinline__ unsigned oob_unless(unsigned off, int ok) { return (off & ~WGRAD_OOB) | ((unsigned)(ok - 1) & WGRAD_OOB); }
+#include "conv_rows.h"                            // CONV_OOB, oob_unless, region_yx (shared with the forward / data-gradient kernels)
 
 // gfx950's transposing LDS read: ds_read_b64_tr_b16 gives lane c of a 16-lane group the 4 k-values of channel c0 + c when lane p
 // of the group points at row k0 + p/4, channels c0 + 4 (p%4) .. +3.  No register transposes, no row permutation.
@@ -80,11 +76,11 @@ __device__ __forceinline__ WgradItem wgrad_item(const P &p) {
 template <bool REGION, class P>
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t wgrad_dy_rsrc(const P &p, const WgradItem &it) {
     const long first = REGION ? (long)it.n_first * p.Ho * p.Wo : it.kbeg;
-    return __builtin_amdgcn_make_buffer_rsrc((void *)(p.DY + first * p.dy_pitch), 0, (int)WGRAD_OOB, 0x00020000);
+    return __builtin_amdgcn_make_buffer_rsrc((void *)(p.DY + first * p.dy_pitch), 0, (int)CONV_OOB, 0x00020000);
 }
 template <class P>
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t wgrad_x_rsrc(const P &p, const WgradItem &it) {
-    return __builtin_amdgcn_make_buffer_rsrc((void *)(p.X + (long)it.n_first * p.H * p.W * p.x_pitch), 0, (int)WGRAD_OOB, 0x00020000);
+    return __builtin_amdgcn_make_buffer_rsrc((void *)(p.X + (long)it.n_first * p.H * p.W * p.x_pitch), 0, (int)CONV_OOB, 0x00020000);
 }
 
 // ----------------------------------------------------------------------------------------------------------- pixel walk
